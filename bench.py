@@ -14,8 +14,8 @@
     BASELINE.json configuration 3: Panda, GLOBAL batch 2^20 sharded by rows over the ranks (131 072 per GPU at N = 8),
     one step = FK(end effector) + RNEA inverse dynamics through `drm_fk_rnea` (one fused launch) + the exchange `--gather`
     names: none (default headline: the outputs stay sharded — the MPC / particle case, strong scaling of the compute), tau /
-    all (`all_gather_into_tensor` of the torques / of tau + pos + quat, 28 / 56 B per row), root (gather to rank 0).  Every
-    mode is timed in the same run (`gather_modes`) with the xGMI estimate beside it (`gather_model_us`): at N = 8 the shard's
+    all (`all_gather_into_tensor` of the torques / of tau + pos + quat, 28 / 56 B per row), root (gather to rank 0).  With
+    --full every mode is timed in the same run (`gather_modes`) with the xGMI estimate beside it (`gather_model_us`): at N = 8 the shard's
     7.3 MB take ~48 us over one 153 GB/s link against ~5.5 us of compute, so `all` is predicted SLOWER than one GPU doing the
     whole batch (~30 us) — the number to quote for a sharded consumer is `none`.  The compute runs the robot's OWN kernel
     (model.specialize(): Panda's constants folded into the instruction stream, hipcc at run time; `--library-kernels` for the
@@ -30,7 +30,12 @@ and `--no-graph` launches eagerly.
 HIP events on the launch stream around the timed region give the average duration of a launch for the roofline
 object.
 
-The JSON line also carries
+A plain run (either config) sets up, warms up, times the K steps of its headline by the wall clock and prints the line
+(`metric`, `value`, `unit`, `ms_per_step`, ...); the HIP-event passes and every other leg are --full.  `--dump-outputs DIR`
+writes what the last timed step computed (pos, quat, lin_jac, ang_jac; --config 3: tau, pos, quat of rank 0's rows) as
+DIR/<name>.npy, from inputs that are the same in every run with the same arguments.
+
+With --full the JSON line also carries
   "roofline":       algorithmic bytes (224 B/eval) / average launch duration vs the 8 TB/s HBM peak at the
                     metric batch (which is Infinity-Cache resident: 14.7 MB per launch replayed over the same buffers);
                     with fewer than 200 steps a "steady_state" entry adds the same launch measured over a region of 200
@@ -61,6 +66,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md (6.3 TB/s achievable)
 EE_LINK = {"panda_no_gripper": "panda_virtual_ee_link", "iiwa7": "iiwa_link_ee"}
 CONFIG3_GLOBAL_BATCH = 1 << 20
+DUMP_LIMIT = 64 << 20     # bytes of --dump-outputs
 
 
 def parse_args(argv=None):
@@ -106,6 +112,16 @@ def parse_args(argv=None):
     ap.add_argument("--verify-gather", action="store_true",
                     help="after the timed region, rank 0 recomputes ALL ranks' rows in one single-rank launch and compares the "
                          "gathered buffer with it bit for bit (gather_verified in the JSON line)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the HIP-event pass and `roofline` (with `steady_state` below 200 "
+                         "steps), the counter traffic, roofline_large, the CPU baseline and the reference, the `configs` legs; "
+                         "--config 3: the compute-only region and every exchange mode (`gather_modes`).  "
+                         "The --no-* switches and --configs select among these.  Without it a run sets up, warms up, times the "
+                         "K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last step computed (the arrays a caller receives) as "
+                         "DIR/<name>.npy in float32; at most %d MB in all, a fixed seeded sample of rows beyond that"
+                         % (DUMP_LIMIT >> 20))
     args = ap.parse_args(argv)
     if args.shared_gpu:
         args.backend = "gloo"
@@ -262,10 +278,28 @@ def sample_q(model, B, device, seed):
     return (lo + (hi - lo) * torch.rand(B, len(lim), device=device, generator=gen)).contiguous(), gen
 
 
-def timed_graph_region(launch, K, stream, barrier, use_graph=True, warm_replays=2):
+def dump_outputs(folder, arrays, seed=0):
+    """--dump-outputs: `arrays` (name -> tensor, rows first) as folder/<name>.npy in float32.  Beyond DUMP_LIMIT bytes in all, the
+    same fixed seeded sample of rows of every array (sorted row indices, also written as rows.npy)."""
+    import numpy as np
+    import torch
+    os.makedirs(folder, exist_ok=True)
+    host = {k: t.detach().float().cpu() for k, t in arrays.items()}
+    total = sum(t.numel() * 4 for t in host.values())
+    rows = min(t.shape[0] for t in host.values())
+    if total > DUMP_LIMIT:
+        keep = int((DUMP_LIMIT - 4096) // (total / rows + 8))    # (8 bytes a row for rows.npy, room for the .npy headers)
+        pick = torch.randperm(rows, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+        host = {k: t[pick] for k, t in host.items()}
+        host["rows"] = pick.double()
+    for k, t in host.items():
+        np.save(os.path.join(folder, k + ".npy"), t.numpy().astype(np.float64 if k == "rows" else np.float32))
+
+
+def timed_graph_region(launch, K, stream, barrier, use_graph=True, warm_replays=2, events=True):
     """EXACTLY K launches between barrier + synchronize on both sides, twice: once timed by the host's clock (wall seconds),
-    once more with HIP events on the launch stream around them (device seconds); returns (wall, device, whether a hipGraph was
-    used)."""
+    once more with HIP events on the launch stream around them (device seconds; `events=False`: not run, None); returns (wall,
+    device, whether a hipGraph was used)."""
     import torch
     graph = None
     if use_graph:
@@ -289,8 +323,9 @@ def timed_graph_region(launch, K, stream, barrier, use_graph=True, warm_replays=
         except Exception as err:  # pragma: no cover - depends on the runtime
             print("hipGraph capture failed (%s); launching eagerly" % err, file=sys.stderr)
             graph = None
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record(stream); ev1.record(stream)   # untimed: an event's first record creates it (~10 us on this stack)
+    if events:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record(stream); ev1.record(stream)   # untimed: an event's first record creates it (~10 us on this stack)
 
     def k_steps():
         if graph is not None:
@@ -308,6 +343,8 @@ def timed_graph_region(launch, K, stream, barrier, use_graph=True, warm_replays=
     torch.cuda.synchronize()
     t1 = time.perf_counter()    # this rank's K steps are done; the caller takes the MAX over ranks
     barrier()                   # (closing barrier of the bracket: its own latency, ~50 us over 8 GPUs, is not a step)
+    if not events:
+        return t1 - t0, None, graph is not None
     # (2) the same K steps once more, same bracket, with HIP events on the launch stream around them: the device-side duration
     # (the roofline's launch time).  A graph launch carries ~9 us of its own on the device (4.2 us per step at --steps 20
     # against 3.8 at 200; submitting the timed pass behind two untimed ones, so that the device never idles, does not change
@@ -348,10 +385,11 @@ def compact_line(full):
     out["config"] = {k: cfg.get(k) for k in ("workload", "batch_per_gpu", "global_batch", "parallelism", "launch", "gather",
                                              "gather_bytes_per_rank") if k in cfg}
     roof = full.get("roofline", {})
-    out["roofline"] = {k: _num(roof.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic",
-                                                      "algorithmic_bytes_per_launch", "traffic_over_algorithmic", "kernel",
-                                                      "launch_us") if k in roof}
-    out["roofline"]["traffic_measured_in_this_run"] = bool(roof.get("traffic_measured_in_this_run", False))
+    if roof:                            # (--full)
+        out["roofline"] = {k: _num(roof.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic",
+                                                          "algorithmic_bytes_per_launch", "traffic_over_algorithmic", "kernel",
+                                                          "launch_us") if k in roof}
+        out["roofline"]["traffic_measured_in_this_run"] = bool(roof.get("traffic_measured_in_this_run", False))
     if "steady_state" in roof:          # the same launch in a region of 200 (a 20-step region carries one graph-launch latency)
         out["roofline"]["steady_state_launch_us"] = _num(roof["steady_state"]["launch_us"])
         out["roofline"]["steady_state_frac"] = _num(roof["steady_state"]["frac"])
@@ -520,8 +558,13 @@ def run_metric(args, model, link, device, world, rank, ranks_seen, stream, barri
     for _ in range(W):
         step()
     torch.cuda.synchronize()
-    wall, dev_time, graphed = timed_graph_region(step, K, stream, barrier, use_graph=not args.no_graph and gathered is None)
-    wall, dev_time = reduce_max([wall, dev_time])
+    # (a plain run stops at the wall-clock pass: the HIP-event pass of the same K steps feeds `roofline`, one of the --full legs)
+    wall, dev_time, graphed = timed_graph_region(step, K, stream, barrier, use_graph=not args.no_graph and gathered is None,
+                                                 events=args.full)
+    wall, dev_time = reduce_max([wall, dev_time or 0.0])
+    if args.dump_outputs and rank == 0:     # (the outputs of the last step; the gathered rows when the step gathers)
+        dump_outputs(args.dump_outputs, dict(zip(("pos", "quat", "lin_jac", "ang_jac"),
+                                                 gathered if gathered is not None else plan.outputs())))
 
     verified, vs_whole = None, None
     if args.verify_gather and gathered is not None:
@@ -545,13 +588,6 @@ def run_metric(args, model, link, device, world, rank, ranks_seen, stream, barri
             vs_whole = {"bit_equal": all(torch.equal(g, w_) for g, w_ in zip(gathered, whole.outputs())),
                         "max_abs": max(float((g - w_).abs().max()) for g, w_ in zip(gathered, whole.outputs()))}
         verified = bool(ok)
-    bytes_per_eval = 4 * (n + 7 + 6 * n)            # q in; pos, quat, lin_jac, ang_jac out (SURVEY.md §8d)
-    launch_s = dev_time / K                         # average duration of one launch, HIP events on the launch stream
-    achieved = bytes_per_eval * B / launch_s / 1e9
-    traffic, traffic_src = recorded_traffic(B) if args.robot == "panda_no_gripper" else (None, None)
-    measured, why_not = (None, "not requested")
-    if rank == 0 and world == 1 and not args.no_traffic and os.environ.get("DRM_BENCH_CHILD") != "1":
-        measured, why_not = measured_traffic(args, B)     # (after the timed region: the child runs own the GPU meanwhile)
     line = {
         "metric": "FK+Jacobian evals/sec, Panda 7-DoF, batch=65 536 @1/2/4/8 MI355X",
         "value": world * B * K / wall, "unit": "evals/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -565,6 +601,17 @@ def run_metric(args, model, link, device, world, rank, ranks_seen, stream, barri
                    "launch": "hipGraph of K launches (replayed twice untimed first)" if graphed else "eager launches",
                    "gather": bool(gathered is not None),
                    "gather_bytes_per_rank": B * 4 * (7 + 6 * n) if gathered is not None else 0},
+    }
+    if not args.full:
+        return line
+    bytes_per_eval = 4 * (n + 7 + 6 * n)            # q in; pos, quat, lin_jac, ang_jac out (SURVEY.md §8d)
+    launch_s = dev_time / K                         # average duration of one launch, HIP events on the launch stream
+    achieved = bytes_per_eval * B / launch_s / 1e9
+    traffic, traffic_src = recorded_traffic(B) if args.robot == "panda_no_gripper" else (None, None)
+    measured, why_not = (None, "not requested")
+    if rank == 0 and world == 1 and not args.no_traffic and os.environ.get("DRM_BENCH_CHILD") != "1":
+        measured, why_not = measured_traffic(args, B)     # (after the timed region: the child runs own the GPU meanwhile)
+    line.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": measured["bytes"] if measured else traffic,
                      "traffic_unit": "bytes per launch (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE)",
@@ -587,7 +634,7 @@ def run_metric(args, model, link, device, world, rank, ranks_seen, stream, barri
                              "bounded by launch floor (1.66 us) + write-through drain of 12.8 MB (a launch that only moves "
                              "the bytes takes 2.9 us = 0.63, profiles/r02_metric_lab.txt); genuine HBM streaming is in "
                              "roofline_large"},
-    }
+    })
     if graphed and gathered is None:
         line["fixed_overhead_us"] = {
             "value": 9.0, "note": "one hipGraph launch carries ~9 us between its start and its first kernel on this stack; a region "
@@ -773,31 +820,40 @@ def run_config3(args, model, link, device, world, rank, ranks_seen, stream, barr
             exchange(mode)
         return step
 
+    if headline == "p2p" and plan_put is None:
+        sys.exit("bench.py --gather p2p: the one-sided gather needs IPC-mapped peer buffers (%s)" % ("one rank" if world == 1 else "see stderr"))
     step = step_of(headline)
     for _ in range(W):
         step()
     torch.cuda.synchronize()
-    # the compute of a step alone (graph of K launches), then the full step of every exchange mode (compute + collective)
-    _, dev_compute, _ = timed_graph_region(compute, K, stream, barrier, use_graph=not args.no_graph)
+    # --full: the compute of a step alone (graph of K launches), then the full step of every exchange mode (compute + collective),
+    # each with its HIP-event pass.  A plain run times the headline mode's K steps by the wall clock and nothing else.
+    dev_compute = None
+    if args.full:
+        _, dev_compute, _ = timed_graph_region(compute, K, stream, barrier, use_graph=not args.no_graph)
+        (dev_compute,) = reduce_max([dev_compute])
     modes = {}
-    if headline == "p2p" and plan_put is None:
-        sys.exit("bench.py --gather p2p: the one-sided gather needs IPC-mapped peer buffers (%s)" % ("one rank" if world == 1 else "see stderr"))
-    for mode in (["none"] if world == 1 else ["none", "tau", "root", "all"] + (["p2p"] if plan_put is not None else [])):
+    every = ["none"] if world == 1 else ["none", "tau", "root", "all"] + (["p2p"] if plan_put is not None else [])
+    for mode in (every if args.full else [headline]):
         fn = step_of(mode)
         for _ in range(2):
             fn()
         torch.cuda.synchronize()
         # (a step with a collective is launched eagerly: RCCL under stream capture has never run on this stack — no multi-GPU
         # node, and RCCL refuses two ranks on one device — so there is no switch for it)
-        w_, d_, graphed = timed_graph_region(fn, K, stream, barrier, use_graph=mode in ("none", "p2p") and not args.no_graph)
-        w_, d_ = reduce_max([w_, d_])
-        modes[mode] = {"ms_per_step": w_ / K * 1e3, "value": G * K / w_, "step_us_device": d_ / K * 1e6, "hipgraph": bool(graphed),
+        w_, d_, graphed = timed_graph_region(fn, K, stream, barrier, use_graph=mode in ("none", "p2p") and not args.no_graph,
+                                             events=args.full)
+        w_, d_ = reduce_max([w_, d_ or 0.0])
+        modes[mode] = {"ms_per_step": w_ / K * 1e3, "value": G * K / w_, "step_us_device": d_ / K * 1e6 if args.full else None,
+                       "hipgraph": bool(graphed),
                        "gather_bytes_per_rank": 0 if mode == "none" else rows * 4 * (n if mode == "tau" else width),
                        "gather_model_us": gather_model_us(mode, rows * width * 4, rows * n * 4, world)}
         if mode == "p2p":      # the puts ride on the walk: a step should take max(compute, one block over one link), not their sum
             modes[mode]["one_sided"] = True
-    wall, dev_time = modes[headline]["ms_per_step"] * K * 1e-3, modes[headline]["step_us_device"] * K * 1e-6
-    (dev_compute,) = reduce_max([dev_compute])
+        if mode == headline and args.dump_outputs and rank == 0:
+            # rank 0's rows as the headline step left them: the one-sided step writes them into this rank's gathered arrays
+            dump_outputs(args.dump_outputs, dict(zip(("tau", "pos", "quat"), peer.outputs() if mode == "p2p" else plan.outputs())))
+    wall = modes[headline]["ms_per_step"] * K * 1e-3
     verified, vs_whole = None, None
     if args.verify_gather and world > 1:
         # rank 0 rebuilds EVERY rank's inputs (same seeds), runs them as ONE single-rank launch over all 2^20 rows and holds
@@ -856,11 +912,8 @@ def run_config3(args, model, link, device, world, rank, ranks_seen, stream, barr
                 for got, want in zip(peer.gathered(), (tau_w, pos_w, quat_w)):
                     ok &= int(torch.equal(got, want.reshape(got.shape)))
         verified = bool(ok)
-    bytes_per_eval = 4 * (3 * n + n + 7)                                 # q qd qdd in; tau pos quat out = 140 B
-    launch_s = dev_compute / K
-    achieved = bytes_per_eval * rows / launch_s / 1e9
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # the UNMODIFIED reference on this box's host cores in this run, on a bounded sample of rank 0's shard (its RNEA runs
         # ~5e4 evals/s on one core): compute_endeffector_jacobian / compute_inverse_dynamics timings + the HIP path's deviation
         # from the reference's own tau / pos / quat on the first rows
@@ -888,23 +941,30 @@ def run_config3(args, model, link, device, world, rank, ranks_seen, stream, barr
                    "gather": headline if world > 1 else "none",
                    "gather_bytes_per_rank": modes[headline]["gather_bytes_per_rank"]},
         "own_kernel": own_kernel, "own_kernel_unavailable": own_why,
-        "compute_us_per_step": dev_compute / K * 1e6, "step_us_with_gather": dev_time / K * 1e6,
-        "gather_us_per_step": max(0.0, (dev_time - dev_compute) / K * 1e6) if world > 1 else 0.0,
-        "gather_modes": modes,
-        "gather_modes_note": "the same K steps timed once per exchange mode (barrier + synchronize bracket, max over ranks): none = "
-                             "outputs stay sharded on their GPUs (the headline), tau / all = all_gather_into_tensor of the torques / of "
-                             "tau | pos | quat, root = gather to rank 0; gather_model_us = one block over one 153 GB/s xGMI link "
-                             "(distributed.gather_model_us) — what the exchange should add once it runs over RCCL",
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": None,
-                     "kernel": ("drm_fk_rnea_arm_static (this robot's constants folded in, csrc/drm_arm_stream.hpp)"
-                                if own_kernel and rows >= 1024 * 128 else
-                                "drm::fk_rnea_arm2_kernel<8, 7, 7> (two samples per lane)" if rows > 1024 * 64
-                                else "drm::fk_rnea_arm_kernel<8, 7, 7>"), "bytes_per_eval": bytes_per_eval,
-                     "launch_us": launch_s * 1e6,
-                     "note": "the fused kernel alone (hipGraph of K launches, HIP events); RNEA sits at the vector-FP32 / HBM "
-                             "ridge (2.6 kflop per 140 B), see DESIGN.md"},
     }
+    if args.full:
+        dev_time = modes[headline]["step_us_device"] * K * 1e-6
+        bytes_per_eval = 4 * (3 * n + n + 7)                             # q qd qdd in; tau pos quat out = 140 B
+        launch_s = dev_compute / K
+        achieved = bytes_per_eval * rows / launch_s / 1e9
+        line.update({
+            "compute_us_per_step": dev_compute / K * 1e6, "step_us_with_gather": dev_time / K * 1e6,
+            "gather_us_per_step": max(0.0, (dev_time - dev_compute) / K * 1e6) if world > 1 else 0.0,
+            "gather_modes": modes,
+            "gather_modes_note": "the same K steps timed once per exchange mode (barrier + synchronize bracket, max over ranks): "
+                                 "none = outputs stay sharded on their GPUs (the headline), tau / all = all_gather_into_tensor of the "
+                                 "torques / of tau | pos | quat, root = gather to rank 0; gather_model_us = one block over one 153 GB/s "
+                                 "xGMI link (distributed.gather_model_us) — what the exchange should add once it runs over RCCL",
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                         "kernel": ("drm_fk_rnea_arm_static (this robot's constants folded in, csrc/drm_arm_stream.hpp)"
+                                    if own_kernel and rows >= 1024 * 128 else
+                                    "drm::fk_rnea_arm2_kernel<8, 7, 7> (two samples per lane)" if rows > 1024 * 64
+                                    else "drm::fk_rnea_arm_kernel<8, 7, 7>"), "bytes_per_eval": bytes_per_eval,
+                         "launch_us": launch_s * 1e6,
+                         "note": "the fused kernel alone (hipGraph of K launches, HIP events); RNEA sits at the vector-FP32 / HBM "
+                                 "ridge (2.6 kflop per 140 B), see DESIGN.md"},
+        })
     if peer is not None:
         line["one_sided_gather"] = {"in_kernel": bool(own_kernel) and rows >= 1024 * 128,
                                     "note": "drm_fk_rnea_put: the arm's own fused kernel stores every tile to the peers' gathered arrays "

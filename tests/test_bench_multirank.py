@@ -19,18 +19,20 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from helpers import quat_close  # noqa: E402
 
-def run_bench(*flags, timeout=600):
-    """Run bench.py; check the stdout contract (exactly ONE compact, strict-JSON line from rank 0) and return the FULL record of the
-    run (--detail), which carries the compact line's fields and everything they were cut from."""
+
+def run_bench(*flags, timeout=600, with_full=True):
+    """Run bench.py (with --full unless `with_full` is False); check the stdout contract (exactly ONE compact, strict-JSON line from rank
+    0) and return the FULL record of the run (--detail), which carries the compact line's fields and everything they were cut from."""
     import tempfile
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):   # the spawn path, not an inherited rendezvous
         env.pop(k, None)
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, "detail.json")
-        done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail", detail] + list(flags), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, timeout=timeout, env=env, cwd=ROOT)
+        done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail", detail] + ["--full"] * with_full + list(flags),
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, env=env, cwd=ROOT)
         out = done.stdout.decode()
         every = [l for l in out.splitlines() if l.strip()]
         lines = [l for l in every if l.startswith("{")]      # (gloo's C++ side prints "[Gloo] Rank r is connected ..." to stdout)
@@ -41,7 +43,7 @@ def run_bench(*flags, timeout=600):
         with open(detail) as f:
             full = json.load(f)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-                "dtype", "data", "config", "roofline", "ranks_seen"):
+                "dtype", "data", "config", "ranks_seen") + ("roofline",) * with_full:      # (roofline: a --full leg)
         assert key in compact, key
         if key not in ("config", "roofline"):
             assert compact[key] == full[key] or abs(compact[key] - full[key]) <= 1e-6 * abs(full[key]), key
@@ -98,6 +100,98 @@ def test_gather_flag_per_config():
     assert gather_model_us("none", shard, tau, 8) == 0.0 and gather_model_us("all", shard, tau, 1) == 0.0
     assert abs(gather_model_us("all", shard, tau, 8) - 47.97) < 0.1 and abs(gather_model_us("tau", shard, tau, 8) - 23.99) < 0.1
     assert gather_model_us("root", shard, tau, 8) == gather_model_us("all", shard, tau, 8)
+
+
+def test_full_and_dump_outputs_flags():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_stays_within_its_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 arrays, whole when they fit; beyond the limit the SAME seeded sample of rows of every array
+    (rows.npy), the same sample on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+    arrays = {"pos": torch.rand(5000, 3, generator=torch.Generator().manual_seed(0)),
+              "lin_jac": torch.rand(5000, 3, 7, dtype=torch.float64, generator=torch.Generator().manual_seed(1))}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["lin_jac.npy", "pos.npy"]
+    got = np.load(tmp_path / "whole" / "lin_jac.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, arrays["lin_jac"].float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 << 10)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 10
+    rows = np.load(tmp_path / "a" / "rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 5000 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "pos.npy"), arrays["pos"].numpy()[rows])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """The plain form `--gpus 1 --steps K --warmup W`: the headline fields, none of the --full legs, and with --dump-outputs the
+    outputs of the timed path, the same in two runs (same seeded inputs)."""
+    import numpy as np
+    lines = [run_bench("--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / d), with_full=False)
+             for d in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 7 and line["warmup"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "evals/s"
+        assert line["value"] == pytest.approx(65536 * 1e3 / line["ms_per_step"], rel=1e-6)
+        assert not {"roofline", "roofline_large", "cpu_baseline", "configs"} & set(line)
+    shapes = {"pos": (65536, 3), "quat": (65536, 4), "lin_jac": (65536, 3, 7), "ang_jac": (65536, 3, 7)}
+    for name, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.shape == shape and a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), name
+    quat = np.load(tmp_path / "a" / "quat.npy")
+    assert np.abs(np.linalg.norm(quat, axis=-1) - 1).max() < 1e-5
+    # the values: the fp64 oracle on the bench's own inputs (sample_q, seed 1234 + rank), rows from both ends and a seeded sample
+    import bench
+    model, orc, rows = _oracle_of_bench_robot()
+    q = bench.sample_q(model, 65536, "cuda", 1234)[0][rows].cpu().numpy().astype(np.float64)
+    want = orc.fk_jacobian(q, model._name_to_idx_map[bench.EE_LINK["panda_no_gripper"]], np.float64)
+    got = [np.load(tmp_path / "a" / (name + ".npy"))[rows] for name in ("pos", "quat", "lin_jac", "ang_jac")]
+    assert np.abs(got[0] - want[0]).max() < 1e-5 and quat_close(got[1], want[1], 1e-5)[0]
+    assert np.abs(got[2] - want[2]).max() < 1e-5 and np.abs(got[3] - want[3]).max() < 1e-5
+
+
+def _oracle_of_bench_robot(n_rows=1 << 16):
+    """The bench's robot on cuda, the fp64 oracle of it and the rows a dump is checked on (both ends + a seeded sample)."""
+    import numpy as np
+
+    from helpers import load_model
+    from oracle import Oracle
+    model = load_model("panda_no_gripper", "cuda")
+    rows = np.unique(np.concatenate([np.arange(256), np.arange(n_rows - 256, n_rows),
+                                     np.random.default_rng(0).integers(0, n_rows, 512)]))
+    return model, Oracle(model._spec), rows
+
+
+@pytest.mark.gpu
+def test_plain_config3_run_dumps_the_fused_step(tmp_path):
+    """`--config 3` without --full: the headline mode's K steps only (no gather_modes, no roofline), and with --dump-outputs the
+    fused FK + inverse-dynamics step's tau, pos and quat, against the fp64 oracle on the bench's own inputs (config3_inputs)."""
+    import numpy as np
+
+    import bench
+    G = bench.CONFIG3_GLOBAL_BATCH
+    line = run_bench("--gpus", "1", "--config", "3", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path), with_full=False)
+    assert line["steps"] == 4 and line["scaling"] == "strong" and line["value"] == pytest.approx(G * 1e3 / line["ms_per_step"], rel=1e-6)
+    assert not {"roofline", "gather_modes", "compute_us_per_step", "cpu_baseline"} & set(line)
+    tau, pos, quat = (np.load(tmp_path / (name + ".npy")) for name in ("tau", "pos", "quat"))
+    assert tau.shape == (G, 7) and pos.shape[0] == G and quat.shape[0] == G and tau.dtype == np.float32
+    model, orc, rows = _oracle_of_bench_robot(G)
+    q, qd, qdd = (t[rows].cpu().numpy().astype(np.float64) for t in bench.config3_inputs(model, G, "cuda", 4321))
+    link = model._name_to_idx_map[bench.EE_LINK["panda_no_gripper"]]
+    want_tau = orc.rnea(q, qd, qdd, True, True, np.float64)
+    want_pos, want_quat = orc.fk(q, [link], np.float64)
+    assert (np.abs(tau[rows] - want_tau) / (1 + np.abs(want_tau))).max() < 1e-4
+    assert np.abs(pos[rows].reshape(-1, 3) - want_pos[:, 0]).max() < 1e-5
+    assert quat_close(quat[rows].reshape(-1, 4), want_quat[:, 0], 1e-5)[0]
 
 
 @pytest.mark.gpu

@@ -946,7 +946,7 @@ def test_fused_plan_writes_into_caller_owned_output_blocks():
 # ------------------------------------------------------------------ bench.py: the JSON line the round driver reads
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract_fields(tmp_path):
-    """`python bench.py --gpus 1 --steps K --warmup W` prints ONE compact JSON line (< 4 KB, strict JSON: round 5's 21 KB line was
+    """`python bench.py --gpus 1 --steps K --warmup W --full` prints ONE compact JSON line (< 4 KB, strict JSON: round 5's 21 KB line was
     not readable by the round driver) with the driver's fields, the roofline object of the dominant kernel, the CPU baseline and one
     flat number per BASELINE configuration; the full record of the run goes to --detail."""
     import json
@@ -955,8 +955,8 @@ def test_bench_line_carries_the_contract_fields(tmp_path):
     import sys
     bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
     detail = str(tmp_path / "bench_detail.json")
-    r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-large", "--cpu-seconds", "1",
-                        "--detail", detail], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-large", "--cpu-seconds",
+                        "1", "--detail", detail], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1

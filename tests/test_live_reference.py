@@ -1,128 +1,101 @@
-"""The UNMODIFIED reference, imported and run HERE (CPU, where /root/reference exists), side by side with this package's model on
-`device="cpu"` (libdrm_cpu.so: the kernels' per-sample arithmetic compiled by g++) — the way the reference's own suite exercises
-its model (tests/test_kinematics_dynamics.py:133-137, 325-511: build the model on the CPU, random joint states, every public
-method), on joint states no committed fixture holds.  Skipped where the reference tree is absent (the GPU box): the fixtures
-(tests/golden/*.npz, generated by the same import) carry the comparison there.
+"""The UNMODIFIED reference side by side with this package's model on `device="cpu"` (libdrm_cpu.so: the kernels' per-sample
+arithmetic compiled by g++) — the way the reference's own suite exercises its model (tests/test_kinematics_dynamics.py:133-137,
+325-511: build the model on the CPU, random joint states, every public method).  What the reference returned is recorded in
+tests/golden/golden_live.npz (tests/golden/make_golden_live.py imports the reference and runs it on these joint states), so the
+comparison runs wherever the suite does.
 
 Forward: FK and the Jacobian of EVERY link, inverse dynamics (4 flag combinations), non-linear effects, the inertia matrix,
 forward dynamics.  Reverse mode: the gradients torch autograd produces through the reference for a loss on each output, with
 respect to the joint state and to learnable link parameters, against the hand-written backward.  Tolerances as in the fixtures'
 tests (helpers.TOL_*)."""
-import contextlib
-import io
 import os
 
 import numpy as np
 import pytest
 import torch
 
-import ref_import
-from helpers import TOL_TAU, load_model, max_err, quat_close
-
-pytestmark = pytest.mark.skipif(not ref_import.reference_available(), reason="the reference tree is not on this machine")
+from helpers import GOLDEN_DIR, TOL_TAU, load_model, max_err, quat_close
 
 ROBOTS = ["2link_robot", "panda_no_gripper", "iiwa7", "panda", "jaco", "allegro_left", "trifinger_edu", "fetch_arm_no_gripper", "fetch"]
-REL = {"2link_robot": "2link_robot.urdf", "panda_no_gripper": "panda_description/urdf/panda_no_gripper.urdf",
-       "iiwa7": "kuka_iiwa/urdf/iiwa7.urdf", "panda": "panda_description/urdf/panda.urdf", "jaco": "kinova_description/urdf/jaco.urdf",
-       "allegro_left": "allegro/urdf/allegro_hand_description_left.urdf", "trifinger_edu": "trifinger_edu_description/trifinger_edu.urdf",
-       "fetch_arm_no_gripper": "fetch_description/urdf/fetch_arm_no_gripper.urdf", "fetch": "fetch_description/urdf/fetch.urdf"}
 
 
-def reference_model(robot):
-    rm = ref_import.import_reference()
-    path = os.path.join(ref_import.reference_data_dir(), REL[robot])
-    if not os.path.exists(path):
-        pytest.skip("%s is not among the reference's robots" % REL[robot])
-    with contextlib.redirect_stdout(io.StringIO()):
-        return rm.DifferentiableRobotModel(path)
-
-
-def states(model, B, seed):
-    lim = model.get_joint_limits()
-    lo = torch.tensor([j["lower"] for j in lim]); hi = torch.tensor([j["upper"] for j in lim])
-    g = torch.Generator().manual_seed(seed)
-    n = len(lim)
-    q = lo + (hi - lo) * torch.rand(B, n, generator=g)
-    return q, torch.rand(B, n, generator=g) * 2 - 1, torch.rand(B, n, generator=g) * 4 - 2, torch.rand(B, n, generator=g) * 2 - 1
+def live():
+    """tests/golden/golden_live.npz: the reference's outputs for these tests (tests/golden/make_golden_live.py)."""
+    return np.load(os.path.join(GOLDEN_DIR, "golden_live.npz"), allow_pickle=False)
 
 
 @pytest.mark.parametrize("robot", ROBOTS)
 def test_every_public_method_next_to_the_reference(robot, cpu_library):
-    ref = reference_model(robot)
+    g, key = live(), "every/%s/" % robot
     m = load_model(robot, "cpu")
-    assert m._n_dofs == ref._n_dofs and [b.name for b in m._bodies] == [b.name for b in ref._bodies]
-    B = 9
-    q, qd, qdd, f = states(ref, B, seed=20260927)
+    assert m._n_dofs == int(g[key + "n_dofs"]) and [b.name for b in m._bodies] == g[key + "bodies"].tolist()
+    q, qd, qdd, f = (torch.from_numpy(g[key + name]) for name in ("q", "qd", "qdd", "f"))
     with torch.no_grad():
-        for link in [b.name for b in ref._bodies][1:]:
-            rp, rq = ref.compute_forward_kinematics(q, link)
-            rl, ra = ref.compute_endeffector_jacobian(q, link)
+        for link in g[key + "bodies"].tolist()[1:]:
+            rp, rq, rl, ra = (g["%s%s/%s" % (key, name, link)] for name in ("pos", "quat", "lin", "ang"))
             pos, quat = m.compute_forward_kinematics(q, link)
             lin, ang = m.compute_endeffector_jacobian(q, link)
-            assert max_err(pos.numpy(), rp.numpy()) < 2e-6 and quat_close(quat.numpy(), rq.numpy(), 2e-6)[0], (robot, link)
-            assert max_err(lin.numpy(), rl.numpy()) < 2e-6 and max_err(ang.numpy(), ra.numpy()) < 2e-6, (robot, link)
+            assert max_err(pos.numpy(), rp) < 2e-6 and quat_close(quat.numpy(), rq, 2e-6)[0], (robot, link)
+            assert max_err(lin.numpy(), rl) < 2e-6 and max_err(ang.numpy(), ra) < 2e-6, (robot, link)
         for grav in (True, False):
             for damp in (True, False):
-                want = ref.compute_inverse_dynamics(q, qd, qdd, include_gravity=grav, use_damping=damp)
+                want = g[key + "tau_g%d_d%d" % (grav, damp)]
                 got = m.compute_inverse_dynamics(q, qd, qdd, include_gravity=grav, use_damping=damp)
-                assert np.allclose(got.numpy(), want.numpy(), **TOL_TAU), (robot, grav, damp)
-        assert np.allclose(m.compute_non_linear_effects(q, qd).numpy(), ref.compute_non_linear_effects(q, qd).numpy(), **TOL_TAU)
-        H = ref.compute_lagrangian_inertia_matrix(q)
-        assert np.allclose(m.compute_lagrangian_inertia_matrix(q).numpy(), H.numpy(), atol=5e-5, rtol=2e-5), robot
-        want = ref.compute_forward_dynamics(q, qd, f.clone(), include_gravity=True, use_damping=True)     # (the reference edits f in place)
+                assert np.allclose(got.numpy(), want, **TOL_TAU), (robot, grav, damp)
+        assert np.allclose(m.compute_non_linear_effects(q, qd).numpy(), g[key + "nle"], **TOL_TAU)
+        H = g[key + "H"]
+        assert np.allclose(m.compute_lagrangian_inertia_matrix(q).numpy(), H, atol=5e-5, rtol=2e-5), robot
+        want = torch.from_numpy(g[key + "qdd_fd"])
         got = m.compute_forward_dynamics(q, qd, f, include_gravity=True, use_damping=True)
         rel = (got - want).abs() / (1.0 + want.abs())
         assert float(rel.max()) < (1e-4 if robot in ("panda_no_gripper", "iiwa7", "2link_robot", "fetch_arm_no_gripper") else 1e-3), robot
 
 
-def _learnable_pair(robot, link, names):
-    """The reference and this package's CPU model with the same learnable parameters on `link`, identically initialised."""
-    ref, m = reference_model(robot), load_model(robot, "cpu")       # (first: it puts the reference on sys.path)
-    import differentiable_robot_model.rigid_body_params as ref_params
+def _learnable(g, key, robot, link, names):
+    """This package's CPU model with learnable `names` on `link`, initialised to the values the reference run started from."""
     from differentiable_robot_model_amd import rigid_body_params as own_params
-    pairs = []
+    m = load_model(robot, "cpu")
+    mods = []
     for pname in names:
         torch.manual_seed(7)
-        make = {"trans": lambda mod: mod.UnconstrainedTensor(dim1=1, dim2=3), "rot_angles": lambda mod: mod.UnconstrainedTensor(dim1=1, dim2=3),
-                "mass": lambda mod: mod.PositiveScalar(), "com": lambda mod: mod.UnconstrainedTensor(dim1=1, dim2=3)}[pname]
-        a, b = make(ref_params), make(own_params)
-        b.load_state_dict(a.state_dict())
-        ref.make_link_param_learnable(link, pname, a)
-        m.make_link_param_learnable(link, pname, b)
-        pairs.append((a, b))
-    return ref, m, pairs
+        mod = {"trans": lambda: own_params.UnconstrainedTensor(dim1=1, dim2=3),
+               "rot_angles": lambda: own_params.UnconstrainedTensor(dim1=1, dim2=3),
+               "mass": lambda: own_params.PositiveScalar(), "com": lambda: own_params.UnconstrainedTensor(dim1=1, dim2=3)}[pname]()
+        mod.load_state_dict({pn: torch.from_numpy(g["%sinit/%s/%s" % (key, pname, pn)]) for pn, _ in mod.named_parameters()})
+        m.make_link_param_learnable(link, pname, mod)
+        mods.append((pname, mod))
+    return m, mods
 
 
 @pytest.mark.parametrize("robot,link,ee", [("iiwa7", "iiwa_link_2", "iiwa_link_ee"), ("panda", "panda_link3", "panda_virtual_ee_link"),
                                             ("allegro_left", "link_5.0", "link_7.0_tip")])
 def test_gradients_next_to_the_references_autograd(robot, link, ee, cpu_library):
     """learn_kinematics / learn_dynamics in one step each: the loss, d loss / d q (qd, qdd) and d loss / d parameters."""
+    g, key = live(), "grad/%s/" % robot
+    q, qd, qdd, target = (torch.from_numpy(g[key + name]) for name in ("q", "qd", "qdd", "target"))
     # kinematics: learnable trans and rot_angles, a loss on the end-effector position
-    ref, m, pairs = _learnable_pair(robot, link, ["trans", "rot_angles"])
-    q, qd, qdd, _ = states(ref, 12, seed=5)
-    target = torch.rand(12, 3, generator=torch.Generator().manual_seed(1))
-    grads = []
-    for model in (ref, m):
-        x = q.clone().requires_grad_(True)
-        loss = torch.nn.functional.mse_loss(model.compute_forward_kinematics(x, ee)[0], target)
-        loss.backward()
-        grads.append((loss.item(), x.grad))
-    assert abs(grads[0][0] - grads[1][0]) < 1e-6 and max_err(grads[1][1].numpy(), grads[0][1].numpy()) < 2e-6 * max(1.0, float(grads[0][1].abs().max()))
-    for a, b in pairs:
-        for pa, pb in zip(a.parameters(), b.parameters()):
-            assert max_err(pb.grad.numpy(), pa.grad.numpy()) < 5e-6 * max(1.0, float(pa.grad.abs().max())), (robot, link)
+    m, mods = _learnable(g, key + "kin_", robot, link, ["trans", "rot_angles"])
+    x = q.clone().requires_grad_(True)
+    loss = torch.nn.functional.mse_loss(m.compute_forward_kinematics(x, ee)[0], target)
+    loss.backward()
+    ref_loss, ref_dq = float(g[key + "kin_loss"]), g[key + "kin_dq"]
+    assert abs(ref_loss - loss.item()) < 1e-6 and max_err(x.grad.numpy(), ref_dq) < 2e-6 * max(1.0, float(np.abs(ref_dq).max()))
+    for pname, mod in mods:
+        for pn, pb in mod.named_parameters():
+            pa = g["%skin_grad/%s/%s" % (key, pname, pn)]
+            assert max_err(pb.grad.numpy(), pa) < 5e-6 * max(1.0, float(np.abs(pa).max())), (robot, link)
     # dynamics: learnable mass and com, a loss on the torques
-    ref, m, pairs = _learnable_pair(robot, link, ["mass", "com"])
-    want = torch.rand(12, ref._n_dofs, generator=torch.Generator().manual_seed(2))
-    grads = []
-    for model in (ref, m):
-        xs = [t.clone().requires_grad_(True) for t in (q, qd, qdd)]
-        loss = torch.nn.functional.mse_loss(model.compute_inverse_dynamics(*xs), want)
-        loss.backward()
-        grads.append((loss.item(), [x.grad for x in xs]))
-    assert abs(grads[0][0] - grads[1][0]) <= 1e-5 * max(1.0, grads[0][0])
-    for ga, gb in zip(grads[0][1], grads[1][1]):
-        assert max_err(gb.numpy(), ga.numpy()) <= 2e-4 * max(1.0, float(ga.abs().max())), robot
-    for a, b in pairs:
-        for pa, pb in zip(a.parameters(), b.parameters()):
-            assert max_err(pb.grad.numpy(), pa.grad.numpy()) <= 2e-4 * max(1.0, float(pa.grad.abs().max())), (robot, link)
+    m, mods = _learnable(g, key + "dyn_", robot, link, ["mass", "com"])
+    want = torch.from_numpy(g[key + "want"])
+    xs = [t.clone().requires_grad_(True) for t in (q, qd, qdd)]
+    loss = torch.nn.functional.mse_loss(m.compute_inverse_dynamics(*xs), want)
+    loss.backward()
+    ref_loss = float(g[key + "dyn_loss"])
+    assert abs(ref_loss - loss.item()) <= 1e-5 * max(1.0, ref_loss)
+    for name, x in zip(("q", "qd", "qdd"), xs):
+        ga = g[key + "dyn_d" + name]
+        assert max_err(x.grad.numpy(), ga) <= 2e-4 * max(1.0, float(np.abs(ga).max())), robot
+    for pname, mod in mods:
+        for pn, pb in mod.named_parameters():
+            pa = g["%sdyn_grad/%s/%s" % (key, pname, pn)]
+            assert max_err(pb.grad.numpy(), pa) <= 2e-4 * max(1.0, float(np.abs(pa).max())), (robot, link)

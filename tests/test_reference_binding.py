@@ -1,14 +1,12 @@
 """INTEGRATION.md stub B, executed: differentiable-robot-model_amd/reference_binding.py binds the three hot methods to the C
 ABI from nothing but the per-link dicts `URDFRobotModel.get_body_parameters_from_urdf` returns (the reference's format).
 
-CPU (not gpu): the binding's own table construction against the package's (same constants, same walks), and — where
-/root/reference exists — that the REFERENCE's loader output binds to bit-identical tables.  GPU: drm_fk / drm_fk_jacobian /
+CPU (not gpu): the binding's own table construction against the package's (same constants, same walks), and that the
+REFERENCE's loader output (recorded under tests/golden/) binds to bit-identical tables.  GPU: drm_fk / drm_fk_jacobian /
 drm_rnea called through the binding against the fp64 oracle.
 """
-import contextlib
-import io
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -16,7 +14,7 @@ import torch
 
 from differentiable_robot_model_amd.reference_binding import HipBinding, bind_reference_model, link_table
 from differentiable_robot_model_amd.urdf_utils import URDFRobotModel
-from helpers import TOL_JAC, TOL_POS, TOL_QUAT, TOL_TAU, load_model, quat_close, sample_states, urdf_path
+from helpers import GOLDEN_DIR, TOL_JAC, TOL_POS, TOL_QUAT, TOL_TAU, load_model, quat_close, sample_states, urdf_path
 from oracle import Oracle
 
 ROBOTS = ["panda_no_gripper", "iiwa7", "allegro_left", "trifinger_edu"]
@@ -40,16 +38,19 @@ def test_binding_tables_equal_the_package_model(robot):
     assert torch.equal(b2.table, b.table)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/differentiable_robot_model"), reason="needs /root/reference (build container)")
 def test_binding_takes_the_references_own_loader_output():
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import ref_import
-    rm = ref_import.import_reference()
-    path = os.path.join(ref_import.reference_data_dir(), "panda_description/urdf/panda_no_gripper.urdf")
-    with contextlib.redirect_stdout(io.StringIO()):
-        ref_model = rm.DifferentiableRobotModel(path)
-    b = bind_reference_model(ref_model)
-    assert torch.equal(b.table, load_model("panda_no_gripper")._link_table())
+    """The per-link dicts the REFERENCE's URDF loader returns for the Panda (tests/golden/golden_live_loader.json, recorded by
+    tests/golden/make_golden_live.py) bind to the package model's table bit for bit."""
+    with open(os.path.join(GOLDEN_DIR, "golden_live_loader.json")) as f:
+        rec = json.load(f)
+
+    def value(v):
+        if isinstance(v, dict) and "tensor" in v:
+            return torch.tensor(v["tensor"], dtype=getattr(torch, v["dtype"]))
+        return {k: value(x) for k, x in v.items()} if isinstance(v, dict) else v
+    params = [{k: value(v) for k, v in p.items()} for p in rec["body_params"]]
+    b = HipBinding(params, rec["parents"], "cpu")
+    assert torch.equal(b.table, load_model(rec["robot"])._link_table())
 
 
 @pytest.mark.gpu

@@ -1,5 +1,7 @@
 """Inertia-matrix parametrisations (rigid_body_params.py): constructions, initialisation from a target matrix, and
-equality with the reference's modules for the same parameter values (when /root/reference is present)."""
+equality with the reference's modules for the same parameter values (recorded under tests/golden/)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -7,12 +9,7 @@ import torch
 from differentiable_robot_model_amd.rigid_body_params import (CovParameterized3DInertiaMatrixNet, PositiveScalar,
                                                               Symm3DInertiaMatrixNet, SymmPosDef3DInertiaMatrixNet,
                                                               TriangParam3DInertiaMatrixNet)
-
-try:
-    import ref_import
-    HAVE_REF = ref_import.reference_available()
-except Exception:  # pragma: no cover
-    HAVE_REF = False
+from helpers import GOLDEN_DIR
 
 TARGET = torch.tensor([[0.031, 0.002, -0.004], [0.002, 0.045, 0.003], [-0.004, 0.003, 0.052]])
 
@@ -48,24 +45,20 @@ def test_positive_scalar_starts_at_the_requested_value():
     assert abs(p().item() - 2.0) < 1e-6
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
 @pytest.mark.parametrize("name", ["Symm3DInertiaMatrixNet", "SymmPosDef3DInertiaMatrixNet",
                                   "CovParameterized3DInertiaMatrixNet"])
 def test_same_parameters_same_matrix_as_the_reference(name):
-    ref_import.import_reference()
-    import differentiable_robot_model.rigid_body_params as ref_rbp
+    """Against the reference's modules (tests/golden/golden_live.npz, recorded by tests/golden/make_golden_live.py)."""
     import differentiable_robot_model_amd.rigid_body_params as my_rbp
-    torch.manual_seed(1)
+    g = np.load(os.path.join(GOLDEN_DIR, "golden_live.npz"), allow_pickle=False)
     kw = {} if name == "Symm3DInertiaMatrixNet" else {"bias": 1e-6}
-    ref = getattr(ref_rbp, name)(init_param_std=0.2, **kw)
     mine = getattr(my_rbp, name)(**kw)
     with torch.no_grad():
-        mine.l.copy_(ref.l)
-    assert torch.allclose(mine(), ref(), atol=1e-7)
+        mine.l.copy_(torch.from_numpy(g["rbp/%s/l" % name]))
+    assert torch.allclose(mine(), torch.from_numpy(g["rbp/%s/matrix" % name]), atol=1e-7)
     # initialisation from a matrix stores the same six numbers
-    ref2 = getattr(ref_rbp, name)(init_param=TARGET.reshape(1, 3, 3), **kw)
     mine2 = getattr(my_rbp, name)(init_param=TARGET.reshape(1, 3, 3), **kw)
-    assert torch.allclose(mine2.l, ref2.l, atol=1e-6)
+    assert torch.allclose(mine2.l, torch.from_numpy(g["rbp/%s/l_from_target" % name]), atol=1e-6)
 
 
 def test_batched_matrix_helpers_match_the_reference_layout():

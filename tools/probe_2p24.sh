@@ -4,7 +4,7 @@
 #   2. rocprofv3 --pmc passes at 2^22 and 2^24: address translation (UTCL1), L2 -> fabric write / read stalls
 # Run on the GPU box: bash tools/probe_2p24.sh  -> gpurun_out/p24/
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/p24; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-B="python $ROOT/bench.py --no-cpu-baseline --no-traffic --no-configs --no-large --steps 20 --warmup 3"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-traffic --no-configs --no-large --steps 20 --warmup 3"
 for batch in 4194304 4000000 8388608 8000000 12582912 16777216 16000000 16777152 20000000; do
   $B --batch $batch 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']

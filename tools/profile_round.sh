@@ -12,16 +12,16 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-B="python $ROOT/bench.py --no-cpu-baseline --no-traffic --detail /dev/null"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-traffic --detail /dev/null"
 BM="$B --no-configs"   # the metric leg alone (counter passes, per-batch stats)
 # round 6: stdout of bench.py is ONE compact line (< 4 KB); the full record goes to --detail.  The default run here is the FULL one
-# (--configs full: the reference beside every leg, counter traffic per leg); the driver's own form (k20) runs the fast legs
-( time python $ROOT/bench.py --configs full --detail $OUT/bench_default_detail.json ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+# (--full --configs full: the reference beside every leg, counter traffic per leg); the plain form (k20) times its steps only
+( time python $ROOT/bench.py --full --configs full --detail $OUT/bench_default_detail.json ) > $OUT/bench_default.json 2> $OUT/bench_default.err
 ( time python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_k20_detail.json ) > $OUT/bench_k20.json 2> $OUT/bench_k20.err
-python $ROOT/bench.py --config 3 --detail $OUT/bench_config3_detail.json > $OUT/bench_config3.json 2> $OUT/bench_config3.err
-python $ROOT/bench.py --gpus 2 --config 3 --gather all --steps 20 --warmup 5 --shared-gpu --verify-gather --no-cpu-baseline --detail $OUT/bench_config3_two_ranks_shared_gpu_detail.json > $OUT/bench_config3_two_ranks_shared_gpu.json 2> $OUT/bench_config3_two_ranks.err
-python $ROOT/bench.py --gpus 2 --config 3 --gather p2p --steps 20 --warmup 5 --shared-gpu --verify-gather --no-cpu-baseline --detail $OUT/bench_config3_p2p_two_ranks_shared_gpu_detail.json > $OUT/bench_config3_p2p_two_ranks_shared_gpu.json 2> $OUT/bench_config3_p2p_two_ranks.err
-python $ROOT/bench.py --gpus 2 --gather --steps 20 --warmup 5 --shared-gpu --verify-gather --no-large --no-cpu-baseline --detail $OUT/bench_metric_two_ranks_shared_gpu_detail.json > $OUT/bench_metric_two_ranks_shared_gpu.json 2> $OUT/bench_metric_two_ranks.err
+python $ROOT/bench.py --full --config 3 --detail $OUT/bench_config3_detail.json > $OUT/bench_config3.json 2> $OUT/bench_config3.err
+python $ROOT/bench.py --full --gpus 2 --config 3 --gather all --steps 20 --warmup 5 --shared-gpu --verify-gather --no-cpu-baseline --detail $OUT/bench_config3_two_ranks_shared_gpu_detail.json > $OUT/bench_config3_two_ranks_shared_gpu.json 2> $OUT/bench_config3_two_ranks.err
+python $ROOT/bench.py --full --gpus 2 --config 3 --gather p2p --steps 20 --warmup 5 --shared-gpu --verify-gather --no-cpu-baseline --detail $OUT/bench_config3_p2p_two_ranks_shared_gpu_detail.json > $OUT/bench_config3_p2p_two_ranks_shared_gpu.json 2> $OUT/bench_config3_p2p_two_ranks.err
+python $ROOT/bench.py --full --gpus 2 --gather --steps 20 --warmup 5 --shared-gpu --verify-gather --no-large --no-cpu-baseline --detail $OUT/bench_metric_two_ranks_shared_gpu_detail.json > $OUT/bench_metric_two_ranks_shared_gpu.json 2> $OUT/bench_metric_two_ranks.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- $B > $OUT/prof_stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats_k20 -- $B --gpus 1 --steps 20 --warmup 5 > $OUT/prof_stats_k20.log 2>&1
 # one stats file per batch size; 65 536 also launched eagerly (graph replays report the tracer's own period, r03_rocprof_overhead.md)
