@@ -625,3 +625,75 @@ class _ForwardDynamics(torch.autograd.Function):
                                                                   any(ctx.needs_input_grad[:2]), ctx.param_mask if want_p else 0)
         return (gq if ctx.needs_input_grad[0] else None), (gqd if ctx.needs_input_grad[1] else None), \
             (gf if ctx.needs_input_grad[2] else None), grad_ops, None, None, None, None, None, None
+
+
+class _RolloutFirstOrderOnly(_FirstOrderOnly):
+    """_FirstOrderOnly for the gradients of a rollout (_ForwardDynamicsRollout): correct to first order, refuses to be differentiated."""
+
+    @staticmethod
+    def backward(ctx, _):
+        raise NotImplementedError(
+            "compute_forward_dynamics_rollout is a first-order node (its backward is a reverse sweep of first-order steps): for second "
+            "derivatives compose the rollout from model.compute_forward_dynamics(q, qd, tau[t]) and the integrator step by step, which "
+            "is differentiable twice with respect to q, qd, tau and the learnable link parameters")
+
+
+class _ForwardDynamicsRollout(torch.autograd.Function):
+    """T steps of forward dynamics and an Euler integrator as ONE autograd node (backend.forward_dynamics_rollout, csrc/drm_rollout.hip).
+
+    Forward: one rollout call that also keeps qdd_t.  Backward: a reverse sweep over the steps, each the per-step VJP of
+    _ForwardDynamics._first_order (two launches).  With cotangents Q, V on (q_{t+1}, qd_{t+1}), after adding the output gradients of
+    step t + 1,
+        semi-implicit Euler (qd' = qd + dt a, q' = q + dt qd'):   V += dt Q,  A = dt V
+        explicit Euler      (q' = q + dt qd, qd' = qd + dt a):    A = dt V,   V += dt Q
+    then (gq, gqd, gtau_t, gtheta) = VJP_FD(q_t, qd_t, qdd_t; A), Q += gq, V += gqd.  Gradients reach q0, qd0, tau and the learnable link
+    parameters; under create_graph=True they are first-order gradients that refuse a second differentiation (_RolloutFirstOrderOnly)."""
+
+    @staticmethod
+    def forward(ctx, q0, qd0, tau, ops_f, dw, dt, gravity, damping, explicit, n_dofs, param_mask):
+        q_traj, qd_traj, qdd_traj = backend.forward_dynamics_rollout(dw.program, ops_f, dw.ops_i, q0, qd0, tau, dt, gravity, damping,
+                                                                     explicit, n_dofs, want_qdd=True)
+        ctx.save_for_backward(q0, qd0, q_traj, qd_traj, qdd_traj, ops_f)
+        ctx.dw, ctx.dt, ctx.flags, ctx.explicit, ctx.n_dofs, ctx.param_mask = dw, float(dt), (gravity, damping), explicit, n_dofs, param_mask
+        ctx.dtypes = (q0.dtype, qd0.dtype, tau.dtype)
+        return q_traj, qd_traj
+
+    @staticmethod
+    def backward(ctx, grad_q_traj, grad_qd_traj):
+        q0, qd0, q_traj, qd_traj, qdd_traj, ops_f = ctx.saved_tensors
+        dw, n, dt, flags = ctx.dw, ctx.n_dofs, ctx.dt, ctx.flags
+        want_p = bool(ctx.needs_input_grad[3]) and ctx.param_mask != 0
+        mask = ctx.param_mask if want_p else 0
+        second = torch.is_grad_enabled()
+        T, B = q_traj.shape[0], q_traj.shape[1]
+        with torch.no_grad():
+            table = ops_f.detach()
+            Q = torch.zeros(B, n, device=q_traj.device, dtype=torch.float32)
+            V = torch.zeros_like(Q)
+            gtau = torch.empty(T, B, n, device=q_traj.device, dtype=torch.float32)
+            gops = None
+            for t in range(T - 1, -1, -1):
+                if grad_q_traj is not None:
+                    Q = Q + grad_q_traj[t].to(torch.float32)
+                if grad_qd_traj is not None:
+                    V = V + grad_qd_traj[t].to(torch.float32)
+                if ctx.explicit:
+                    A = dt * V
+                    V = V + dt * Q
+                else:
+                    V = V + dt * Q
+                    A = dt * V
+                q_t = q0.to(torch.float32) if t == 0 else q_traj[t - 1]
+                qd_t = qd0.to(torch.float32) if t == 0 else qd_traj[t - 1]
+                gq, gqd, gtau_t, gops_t = _ForwardDynamics._first_order(dw, n, flags, q_t, qd_t, qdd_traj[t], table, A, True, mask)
+                Q = Q + gq
+                V = V + gqd
+                gtau[t] = gtau_t
+                if gops_t is not None:
+                    gops = gops_t if gops is None else gops + gops_t
+        out = [Q.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None, V.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None,
+               gtau.to(ctx.dtypes[2]) if ctx.needs_input_grad[2] else None, gops.to(ops_f.dtype) if (want_p and gops is not None) else None]
+        if second:
+            with torch.enable_grad():
+                out = [_RolloutFirstOrderOnly.apply(g.requires_grad_(True)) if g is not None else None for g in out]
+        return tuple(out) + (None,) * 7

@@ -21,9 +21,10 @@ from .flatten import MAX_SEGMENTS, OPI_PERM, WalkProgram
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdrm_hip.so")
 CPU_LIB_PATH = os.path.join(_HERE, "csrc", "libdrm_cpu.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 RNEA_GRAVITY, RNEA_DAMPING = 1, 2
+ROLLOUT_EXPLICIT_EULER = 4    # include/drm_hip.h DRM_ROLLOUT_EXPLICIT_EULER (ABI 14)
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
 
@@ -81,7 +82,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_walk_table_backward", "drm_fk_rnea", "drm_forward_dynamics_scratch_floats", "drm_crba_scratch_floats",
            "drm_rnea_scratch_floats", "drm_fk_mse", "drm_fk_mse_scratch_floats", "drm_rnea_scratch_floats_aligned",
            "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned", "drm_special_load", "drm_fk_rnea_put",
-           "drm_fk_mse_links", "drm_walk_table_links", "drm_walk_table_links_backward")
+           "drm_fk_mse_links", "drm_walk_table_links", "drm_walk_table_links_backward", "drm_forward_dynamics_rollout",
+           "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -169,7 +171,10 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_fk_rnea.argtypes = [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
         lib.drm_fk_rnea_put.restype = ctypes.c_int
         lib.drm_fk_rnea_put.argtypes = [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(DrmPut), vp]
-        for name in ("drm_rnea_scratch_floats_aligned", "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned"):
+        lib.drm_forward_dynamics_rollout.restype = ctypes.c_int
+        lib.drm_forward_dynamics_rollout.argtypes = [wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, vp, vp, vp, vp, vp]
+        for name in ("drm_rnea_scratch_floats_aligned", "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned",
+                     "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
@@ -849,6 +854,39 @@ def forward_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, f, include_gravity:
                                         qdd.data_ptr(), scratch.data_ptr() if scratch is not None else None,
                                         _stream(q.device)), lib)
     return qdd
+
+
+def forward_dynamics_rollout(prog: WalkProgram, ops_f, ops_i, q0, qd0, tau, dt: float, gravity: bool, damping: bool, explicit: bool,
+                             n_dofs: int, want_qdd: bool = False):
+    """(q_traj, qd_traj, qdd_traj or None), each [T, B, n]: T steps of forward dynamics and an Euler integrator from (q0, qd0) [B, n]
+    under the joint torques tau [T, B, n] (time-major; include/drm_hip.h drm_forward_dynamics_rollout)."""
+    lib = _lib_of(q0, "q0", ops_f)
+    q0, qd0 = _dev_f32(q0, "q0", n_dofs), _dev_f32(qd0, "qd0", n_dofs)
+    if not isinstance(tau, torch.Tensor) or tau.ndim != 3 or tau.shape[2] != n_dofs:
+        raise ValueError("tau must be [T, B, %d], got %s" % (n_dofs, tuple(getattr(tau, "shape", ()))))
+    T, B = int(tau.shape[0]), int(q0.shape[0])
+    if qd0.shape[0] != B or tau.shape[1] != B:
+        raise ValueError("q0 / qd0 / tau batch sizes differ")
+    if T < 1:
+        raise ValueError("a rollout takes at least one step (tau has T = %d)" % T)
+    if not (math.isfinite(dt) and dt > 0):
+        raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+    tau = _dev_f32(tau.reshape(T * B, n_dofs), "tau", n_dofs)
+    outs = _outputs(q0.device, *(((T, B, n_dofs),) * (3 if want_qdd else 2)))
+    q_traj, qd_traj = outs[0], outs[1]
+    qdd_traj = outs[2] if want_qdd else None
+    if B == 0:
+        return q_traj, qd_traj, qdd_traj
+    flags = (RNEA_GRAVITY if gravity else 0) | (RNEA_DAMPING if damping else 0) | (ROLLOUT_EXPLICIT_EULER if explicit else 0)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    need = int(lib.drm_forward_dynamics_rollout_scratch_floats_aligned(ctypes.byref(walk), B))    # (_dev_f32 / _outputs: aligned)
+    scratch = torch.empty(need, device=q0.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q0.device):
+        _check(lib.drm_forward_dynamics_rollout(ctypes.byref(walk), q0.data_ptr(), qd0.data_ptr(), tau.data_ptr(), B, T, float(dt), flags,
+                                                q_traj.data_ptr(), qd_traj.data_ptr(),
+                                                qdd_traj.data_ptr() if qdd_traj is not None else None,
+                                                scratch.data_ptr() if scratch is not None else None, _stream(q0.device)), lib)
+    return q_traj, qd_traj, qdd_traj
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

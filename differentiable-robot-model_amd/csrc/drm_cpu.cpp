@@ -15,11 +15,13 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <thread>
 #include <vector>
 
 #include "drm_host_loops.hpp"
 #include "drm_link_forms.hpp"
+#include "drm_rollout.hpp"
 
 namespace {
 using namespace drm_host;
@@ -231,6 +233,39 @@ int drm_forward_dynamics(const drm_walk *w, const float *q, const float *qd, con
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         fd_loop(w, q + b0 * n, qd + b0 * n, f + b0 * n, rows, flags, qdd + b0 * n);
+    });
+    return DRM_OK;
+}
+
+// ABI 14: every chunk of rows runs its T steps on its own (fd_loop, then the integrator of drm_rollout.hpp), the state of step t read
+// back from the slab step t - 1 wrote
+int64_t drm_forward_dynamics_rollout_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_forward_dynamics_rollout_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_forward_dynamics_rollout(const drm_walk *w, const float *q0, const float *qd0, const float *tau, int64_t B, int32_t T, float dt,
+                                 int32_t flags, float *q_traj, float *qd_traj, float *qdd_traj, float *, void *) {
+    if (int rc = check_walk(w)) return rc;
+    if (!q0 || !qd0 || !tau || !q_traj || !qd_traj) return fail(DRM_ERR_INVALID, "q0 / qd0 / tau / q_traj / qd_traj must not be NULL");
+    if (T < 1) return fail(DRM_ERR_INVALID, "a rollout takes at least one step (T = %ld)", (long)T);
+    if (!(dt > 0.0f) || !std::isfinite(dt)) return fail(DRM_ERR_INVALID, "dt must be finite and positive");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    const int n = w->n_dofs, fd_flags = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
+    const bool expl = (flags & DRM_ROLLOUT_EXPLICIT_EULER) != 0;
+    const int64_t slab = B * n;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        std::vector<float> acc(qdd_traj ? 0 : (size_t)rows * n);
+        for (int t = 0; t < T; ++t) {
+            const int64_t off = (int64_t)t * slab + b0 * n;
+            const float *qi = t ? q_traj + off - slab : q0 + b0 * n, *qdi = t ? qd_traj + off - slab : qd0 + b0 * n;
+            float *a = qdd_traj ? qdd_traj + off : acc.data();
+            fd_loop(w, qi, qdi, tau + off, rows, fd_flags, a);
+            for (int64_t i = 0; i < rows * n; ++i) {
+                float x = qi[i], v = qdi[i];
+                drm::rollout_step(x, v, a[i], dt, expl);
+                q_traj[off + i] = x;
+                qd_traj[off + i] = v;
+            }
+        }
     });
     return DRM_OK;
 }

@@ -15,6 +15,7 @@ over tiny torch ops are replaced by:
 There is NO CPU compute path: the compute methods raise if the model does not
 live on a HIP device or if the native library is missing.
 """
+import math
 import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -26,7 +27,7 @@ from . import backend
 from .flatten import (OPF_STRIDE, RobotSpec, WalkProgram, build_robot_spec, build_walk, fold_link_table,
                       foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
-                       _quat_grad_to_rot)
+                       _ForwardDynamicsRollout, _quat_grad_to_rot)
 from .rigid_body import DifferentiableRigidBody, LinkPose, LinkVelocity
 from .urdf_utils import URDFRobotModel
 
@@ -1393,6 +1394,53 @@ class DifferentiableRobotModel(torch.nn.Module):
         if have is None or have[1]._ws_cache is not have[2]:
             self._fast_fd = self._fast_entry("drm_forward_dynamics", "drm_forward_dynamics_scratch_floats_aligned", dw)
         return out
+
+    ROLLOUT_INTEGRATORS = ("semi_implicit_euler", "euler")
+
+    def compute_forward_dynamics_rollout(self, q0: torch.Tensor, qd0: torch.Tensor, tau: torch.Tensor, dt: float,
+                                         integrator: str = "semi_implicit_euler", include_gravity: Optional[bool] = True,
+                                         use_damping: Optional[bool] = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(q_traj, qd_traj) [T, B, n]: the states after steps 1 .. T of a simulation from (q0, qd0) [B, n] under the joint torques
+        tau [T, B, n] (TIME-MAJOR: step t's torques are the contiguous slab tau[t]).  Step t computes
+        qdd_t = compute_forward_dynamics(q_t, qd_t, tau[t], include_gravity, use_damping), then
+            "semi_implicit_euler" (default):   qd_{t+1} = qd_t + dt * qdd_t,  q_{t+1} = q_t + dt * qd_{t+1}
+            "euler" (explicit):                q_{t+1} = q_t + dt * qd_t,     qd_{t+1} = qd_t + dt * qdd_t
+        One launch for 7-DoF arms and hands (the state stays in registers across the steps, csrc/drm_rollout.hip), two per step for
+        every other robot; ``tau`` is never modified.  Unbatched q0, qd0 [n] with tau [T, n] give [T, n].  Differentiable with respect
+        to q0, qd0, tau and the learnable link parameters (one autograd node whose backward sweeps the steps in reverse); first order
+        only: for second derivatives compose compute_forward_dynamics step by step."""
+        if integrator not in self.ROLLOUT_INTEGRATORS:
+            raise ValueError("integrator must be one of %s (got %r)" % (self.ROLLOUT_INTEGRATORS, integrator))
+        for name, t in (("q0", q0), ("qd0", qd0), ("tau", tau)):
+            assert type(t) is torch.Tensor, "%s must be a tensor" % name
+            assert t.device.type == self._device.type, f"Input argument of different device as module: {t}"
+        assert q0.ndim in [1, 2], "Input tensors must have ndim of 1 or 2."
+        assert qd0.shape == q0.shape, "Batch size mismatch between input tensors."
+        assert tau.ndim == q0.ndim + 1, "tau must be [T, B, n] ([T, n] for unbatched q0 / qd0)"
+        assert tau.shape[1:-1] == q0.shape[:-1], "Batch size mismatch between input tensors."
+        assert q0.shape[-1] == self._n_dofs and tau.shape[-1] == self._n_dofs
+        dt = float(dt)
+        if tau.shape[0] < 1:
+            raise ValueError("a rollout takes at least one step (tau has T = 0)")
+        if not (math.isfinite(dt) and dt > 0):
+            raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+        single = q0.ndim == 1
+        if single:
+            q0, qd0, tau = q0.unsqueeze(0), qd0.unsqueeze(0), tau.unsqueeze(1)
+        self._require_device()
+        dw = self._dynamics_walk()
+        ops_f = self._ops_f(dw)
+        explicit = integrator == "euler"
+        if torch.is_grad_enabled() and (ops_f.requires_grad or any(t.requires_grad for t in (q0, qd0, tau))):
+            self._differentiable(dw)
+            q_traj, qd_traj = _ForwardDynamicsRollout.apply(q0, qd0, tau, ops_f, dw, dt, bool(include_gravity), bool(use_damping),
+                                                            explicit, self._n_dofs, self._learnable_op_mask(dw))
+        else:
+            q_traj, qd_traj, _ = backend.forward_dynamics_rollout(dw.program, ops_f, dw.ops_i, q0, qd0, tau, dt, bool(include_gravity),
+                                                                  bool(use_damping), explicit, self._n_dofs)
+        if single:
+            return q_traj[:, 0], qd_traj[:, 0]
+        return q_traj, qd_traj
 
     def compute_forward_dynamics_old(self, q: torch.Tensor, qd: torch.Tensor, f: torch.Tensor,
                                      include_gravity: Optional[bool] = True, use_damping: Optional[bool] = True

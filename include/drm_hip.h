@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define DRM_ABI_VERSION 13
+#define DRM_ABI_VERSION 14
 
 /* ---- layout of one op (= one link) of a walk ---------------------------- */
 #define DRM_SPECIAL_KINDS 16 /* drm_walk.special[] (the kinds not named below are reserved and must be NULL): */
@@ -194,6 +194,8 @@ extern "C" {
 /* flags of drm_rnea */
 #define DRM_RNEA_GRAVITY 1 /* base acceleration (0,0,+9.81)   (robot_model.py:344-350)         */
 #define DRM_RNEA_DAMPING 2 /* tau += damping * qd             (robot_model.py:368-373)         */
+/* flags of drm_forward_dynamics_rollout (ABI 14), beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
+#define DRM_ROLLOUT_EXPLICIT_EULER 4 /* q += dt * qd_t, then qd += dt * qdd_t (default: semi-implicit Euler) */
 
 /* error codes */
 #define DRM_OK 0
@@ -401,6 +403,28 @@ int64_t drm_forward_dynamics_scratch_floats(const drm_walk *walk, int64_t B);
 int64_t drm_forward_dynamics_scratch_floats_aligned(const drm_walk *walk, int64_t B); /* the caller guarantees 16-byte aligned pointers (see Alignment) */
 int drm_forward_dynamics(const drm_walk *walk, const float *q, const float *qd, const float *f, int64_t B,
                          int32_t flags, float *qdd, float *scratch, void *stream);
+
+/*
+ * ABI 14: T steps of forward dynamics and an Euler integrator in one call (sampling-based MPC, fitting dynamics to trajectories,
+ * trajectory optimisation through the dynamics).  Step t = 0 .. T-1 computes qdd_t = drm_forward_dynamics(q_t, qd_t, tau_t)
+ * with the same flags, then
+ *   semi-implicit Euler (default):             qd_{t+1} = qd_t + dt * qdd_t,  q_{t+1} = q_t + dt * qd_{t+1}
+ *   DRM_ROLLOUT_EXPLICIT_EULER:                q_{t+1} = q_t + dt * qd_t,     qd_{t+1} = qd_t + dt * qdd_t
+ * (each update one fused multiply-add).  All arrays are TIME-MAJOR: step t's slab is a contiguous [B, n] array.
+ *   q0, qd0 [B, n], tau [T, B, n]  ->  q_traj, qd_traj [T, B, n]: the states after steps 1 .. T;
+ *   qdd_traj [T, B, n]: qdd_t, or NULL (the backward pass needs it).  tau is not modified.
+ * Full 64-row tiles of 7-DoF arm chains and of hands (DRM_WALK_FINGERS) run ONE kernel that keeps the state in registers across
+ * the T steps (84 B per row and step: tau in, q and qd out; 112 B with qdd_traj); every other robot, the ragged tail of a launch
+ * and misaligned pointers run drm_forward_dynamics on each step's slab followed by a small element-wise integrator kernel.
+ *   scratch   drm_forward_dynamics_rollout_scratch_floats(walk, B) floats: qdd of the composed steps when qdd_traj is NULL, and
+ *             what drm_forward_dynamics asks for; 0 when the fused kernel covers every row (scratch may then be NULL)
+ * DRM_ERR_INVALID for T < 1 or a dt that is not finite and positive; B == 0 returns DRM_OK.  Asynchronous on `stream`.
+ */
+int64_t drm_forward_dynamics_rollout_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_forward_dynamics_rollout_scratch_floats_aligned(const drm_walk *walk, int64_t B); /* 16-byte aligned pointers (see Alignment) */
+int drm_forward_dynamics_rollout(const drm_walk *walk, const float *q0, const float *qd0, const float *tau, int64_t B, int32_t T,
+                                 float dt, int32_t flags, float *q_traj, float *qd_traj, float *qdd_traj, float *scratch,
+                                 void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
