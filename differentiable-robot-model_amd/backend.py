@@ -21,10 +21,11 @@ from .flatten import MAX_SEGMENTS, OPI_PERM, WalkProgram
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdrm_hip.so")
 CPU_LIB_PATH = os.path.join(_HERE, "csrc", "libdrm_cpu.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 RNEA_GRAVITY, RNEA_DAMPING = 1, 2
 ROLLOUT_EXPLICIT_EULER = 4    # include/drm_hip.h DRM_ROLLOUT_EXPLICIT_EULER (ABI 14)
+IK_POSITION_ONLY, IK_COMPOSED = 1, 2     # include/drm_hip.h DRM_IK_POSITION_ONLY / DRM_IK_COMPOSED (ABI 15)
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
 
@@ -83,7 +84,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_rnea_scratch_floats", "drm_fk_mse", "drm_fk_mse_scratch_floats", "drm_rnea_scratch_floats_aligned",
            "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned", "drm_special_load", "drm_fk_rnea_put",
            "drm_fk_mse_links", "drm_walk_table_links", "drm_walk_table_links_backward", "drm_forward_dynamics_rollout",
-           "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned")
+           "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned",
+           "drm_inverse_kinematics", "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -173,8 +175,12 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_fk_rnea_put.argtypes = [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(DrmPut), vp]
         lib.drm_forward_dynamics_rollout.restype = ctypes.c_int
         lib.drm_forward_dynamics_rollout.argtypes = [wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, vp, vp, vp, vp, vp]
+        f32 = ctypes.c_float
+        lib.drm_inverse_kinematics.restype = ctypes.c_int
+        lib.drm_inverse_kinematics.argtypes = [wp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp, vp, i32, vp, vp, vp, vp, vp]
         for name in ("drm_rnea_scratch_floats_aligned", "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned",
-                     "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned"):
+                     "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned",
+                     "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
@@ -887,6 +893,45 @@ def forward_dynamics_rollout(prog: WalkProgram, ops_f, ops_i, q0, qd0, tau, dt: 
                                                 qdd_traj.data_ptr() if qdd_traj is not None else None,
                                                 scratch.data_ptr() if scratch is not None else None, _stream(q0.device)), lib)
     return q_traj, qd_traj, qdd_traj
+
+
+def inverse_kinematics(prog: WalkProgram, ops_f, ops_i, q0, target_pos, target_quat, max_iters: int, damping: float, step: float,
+                       tol_pos: float, tol_rot: float, lower, upper, n_dofs: int, composed: bool = False):
+    """(q [B, n], err [B, 2], iters [B] int32): damped-least-squares IK of the chain walk ``prog``'s target from q0 [B, n] towards
+    target_pos [B, 3] and target_quat [B, 4] (xyzw; None: position only), at most max_iters updates per row
+    (include/drm_hip.h drm_inverse_kinematics).  lower / upper: [n] joint bounds on q0's device, or both None.  ``composed`` forces
+    the composed path (DRM_IK_COMPOSED: tests, A/B)."""
+    lib = _lib_of(q0, "q0", ops_f)
+    q0 = _dev_f32(q0, "q0", n_dofs)
+    target_pos = _dev_f32(target_pos, "target_pos", 3)
+    target_quat = _dev_f32(target_quat, "target_quat", 4) if target_quat is not None else None
+    B = int(q0.shape[0])
+    if target_pos.shape[0] != B or (target_quat is not None and target_quat.shape[0] != B):
+        raise ValueError("q0 / target_pos / target_quat batch sizes differ")
+    if (lower is None) != (upper is None):
+        raise ValueError("lower and upper must be given together")
+    if lower is not None:
+        lower = _dev_f32(lower.reshape(1, n_dofs), "lower", n_dofs)
+        upper = _dev_f32(upper.reshape(1, n_dofs), "upper", n_dofs)
+    q, err = _outputs(q0.device, (B, n_dofs), (B, 2))
+    iters = torch.empty(B, device=q0.device, dtype=torch.int32)
+    if B == 0:
+        return q, err, iters
+    flags = (IK_POSITION_ONLY if target_quat is None else 0) | (IK_COMPOSED if composed else 0)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_IK_COMPOSED takes the composed path on every row: the size for any pointers)
+    query = lib.drm_inverse_kinematics_scratch_floats if composed else lib.drm_inverse_kinematics_scratch_floats_aligned
+    need = int(query(ctypes.byref(walk), B))
+    scratch = torch.empty(need, device=q0.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q0.device):
+        _check(lib.drm_inverse_kinematics(ctypes.byref(walk), q0.data_ptr(), target_pos.data_ptr(),
+                                          target_quat.data_ptr() if target_quat is not None else None, B, int(max_iters),
+                                          float(damping), float(step), float(tol_pos), float(tol_rot),
+                                          lower.data_ptr() if lower is not None else None,
+                                          upper.data_ptr() if upper is not None else None, flags, q.data_ptr(), err.data_ptr(),
+                                          iters.data_ptr(), scratch.data_ptr() if scratch is not None else None,
+                                          _stream(q0.device)), lib)
+    return q, err, iters
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

@@ -21,6 +21,7 @@
 
 #include "drm_host_loops.hpp"
 #include "drm_link_forms.hpp"
+#include "drm_ik.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -264,6 +265,53 @@ int drm_forward_dynamics_rollout(const drm_walk *w, const float *q0, const float
                 drm::rollout_step(x, v, a[i], dt, expl);
                 q_traj[off + i] = x;
                 qd_traj[off + i] = v;
+            }
+        }
+    });
+    return DRM_OK;
+}
+
+// ABI 15: every row runs its iterations on its own: jac_loop of the row, then drm_ik.hpp's update, until it stops
+int64_t drm_inverse_kinematics_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_inverse_kinematics_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_inverse_kinematics(const drm_walk *w, const float *q0, const float *target_pos, const float *target_quat, int64_t B,
+                           int32_t max_iters, float damping, float step, float tol_pos, float tol_rot, const float *lower,
+                           const float *upper, int32_t flags, float *q, float *err, int32_t *iters, float *, void *) {
+    if (int rc = check_walk(w)) return rc;
+    const bool pos_only = (flags & DRM_IK_POSITION_ONLY) != 0;
+    if (!q0 || !target_pos || !q || !err) return fail(DRM_ERR_INVALID, "q0 / target_pos / q / err must not be NULL");
+    if ((target_quat == nullptr) != pos_only) return fail(DRM_ERR_INVALID, "target_quat must be NULL iff DRM_IK_POSITION_ONLY");
+    if ((lower == nullptr) != (upper == nullptr)) return fail(DRM_ERR_INVALID, "lower and upper must be given together");
+    if (max_iters < 0) return fail(DRM_ERR_INVALID, "max_iters must be >= 0");
+    if (!(damping > 0.0f) || !std::isfinite(damping) || !(step > 0.0f) || !std::isfinite(step))
+        return fail(DRM_ERR_INVALID, "damping and step must be finite and positive");
+    if (!(tol_pos >= 0.0f) || !std::isfinite(tol_pos) || !(tol_rot >= 0.0f) || !std::isfinite(tol_rot))
+        return fail(DRM_ERR_INVALID, "tolerances must be finite and >= 0");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    const int n = w->n_dofs;
+    const drm::IkOpts o = {damping * damping, step, tol_pos, tol_rot};
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        std::vector<float> lin(3 * n), ang(3 * n);
+        for (int64_t b = b0; b < b0 + rows; ++b) {
+            float *qr = q + b * n;
+            for (int k = 0; k < n; ++k) qr[k] = q0[b * n + k];
+            float tq[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+            if (!pos_only) {
+                for (int k = 0; k < 4; ++k) tq[k] = target_quat[b * 4 + k];
+                drm::ik_normalize_quat(tq);
+            }
+            auto J = [&](int r, int k) -> float { return r < 3 ? lin[r * n + k] : ang[(r - 3) * n + k]; };
+            auto qf = [&](int k) -> float & { return qr[k]; };
+            for (int i = 0;; ++i) {
+                float p[3], c[4], pos_err, rot_err;
+                jac_loop(w, qr, 1, p, c, lin.data(), ang.data());
+                if (drm::ik_iteration(J, n, p, c, target_pos + b * 3, tq, pos_only, o, i == max_iters, qf, lower, upper, pos_err, rot_err)) {
+                    err[b * 2] = pos_err;
+                    err[b * 2 + 1] = rot_err;
+                    if (iters) iters[b] = i;
+                    break;
+                }
             }
         }
     });

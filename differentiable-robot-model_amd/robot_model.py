@@ -98,6 +98,16 @@ class _DeviceWalk:
     learnable_plan: Optional[tuple] = None   # (learnable links, constant walk table, row selector) of _ops_f_learnable
 
 
+@dataclass
+class InverseKinematicsResult:
+    """What DifferentiableRobotModel.compute_inverse_kinematics returns (no autograd history on any field)."""
+    q: torch.Tensor                     # [B, n] the joint angles where each row stopped
+    pos_err: torch.Tensor               # [B] |target_pos - p| at q
+    rot_err: Optional[torch.Tensor]     # [B] rotation angle between the target and the link's orientation at q; None: position only
+    iterations: torch.Tensor            # [B] int32: the updates applied
+    converged: torch.Tensor             # [B] bool: the errors are within the tolerances
+
+
 class DifferentiableRobotModel(torch.nn.Module):
     """Batched FK / geometric Jacobian / RNEA on MI355X behind the reference API."""
 
@@ -193,7 +203,8 @@ class DifferentiableRobotModel(torch.nn.Module):
                 "_fast_fk": dict, "_fast_jac": dict, "_fast_id": lambda: None, "_fast_crba": lambda: None, "_fast_fd": lambda: None,
                 "_fast_fkid": dict, "_source_plan": lambda: None, "_kin_cache": dict, "_kin_state": lambda: None,
                 "_stream_arg": lambda: None, "_arm_specialized": lambda: False}
-    _DERIVED_LAZY = ("_learnable_sorted", "_skew_any", "_dyn_walk_learnable", "_body_names", "_all_link_idxs", "_fast_links", "_fk_links_plans")
+    _DERIVED_LAZY = ("_learnable_sorted", "_skew_any", "_dyn_walk_learnable", "_body_names", "_all_link_idxs", "_fast_links", "_fk_links_plans",
+                     "_ik_bounds")
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -1441,6 +1452,93 @@ class DifferentiableRobotModel(torch.nn.Module):
         if single:
             return q_traj[:, 0], qd_traj[:, 0]
         return q_traj, qd_traj
+
+    def _joint_bounds(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(lower, upper) [n] float32 on the model device from get_joint_limits(): a DoF whose parsed limits have lower >= upper
+        (a continuous joint, whose <limit> carries no lower / upper) is free, -inf / +inf.  Made once (no copy inside a captured
+        graph)."""
+        have = self.__dict__.get("_ik_bounds")
+        if have is None:
+            lo, hi = [], []
+            for lim in self.get_joint_limits():
+                a, b = float(lim["lower"]), float(lim["upper"])
+                free = not a < b
+                lo.append(-math.inf if free else a)
+                hi.append(math.inf if free else b)
+            have = self._ik_bounds = (torch.tensor(lo, dtype=torch.float32, device=self._device),
+                                      torch.tensor(hi, dtype=torch.float32, device=self._device))
+        return have
+
+    def compute_inverse_kinematics(self, q0: torch.Tensor, link_name: str, target_pos: torch.Tensor,
+                                   target_quat: Optional[torch.Tensor] = None, *, max_iterations: int = 32, damping: float = 0.01,
+                                   step_size: float = 1.0, tol_pos: float = 1e-4, tol_rot: float = 1e-3,
+                                   respect_joint_limits: bool = True, _composed: bool = False) -> InverseKinematicsResult:
+        """Joint angles that put ``link_name`` at target_pos [B, 3] (and at target_quat [B, 4], xyzw as compute_forward_kinematics
+        returns it; None: position only), by damped least squares from q0 [B, n].  Iteration i = 0 .. max_iterations evaluates
+        (p, c, J) = compute_fk_and_jacobian(q_i, link_name) and the errors e_p = target_pos - p and e_R, the rotation vector of
+        target (x) conj(c).  A row stops at q_i when |e_p| <= tol_pos and its rotation angle <= tol_rot, or at i = max_iterations;
+        otherwise q_{i+1} = clamp(q_i + step_size * J^T (J J^T + damping^2 I)^-1 e) (J = [lin_jac; ang_jac], 6 x n; lin_jac alone,
+        3 x n, in position-only mode) between the joint limits of get_joint_limits() (respect_joint_limits; a continuous joint
+        is free).  One kernel launch per solve for 7-DoF arms (csrc/drm_ik.hip), two per iteration for every other robot, never a
+        host synchronisation.  Unbatched q0 [n] with target_pos [3] give unbatched results.
+
+        The results carry NO autograd history, even when the inputs or the learnable link parameters require grad: the solve is
+        not differentiable here.  A model with learnable links solves against their current values.  (``_composed``: every row takes
+        the composed path, DRM_IK_COMPOSED; for tests and A/B measurements.)"""
+        for name, t in (("q0", q0), ("target_pos", target_pos), ("target_quat", target_quat)):
+            if t is None and name == "target_quat":
+                continue
+            if type(t) is not torch.Tensor:
+                raise TypeError("%s must be a tensor" % name)
+            if t.device.type != self._device.type:
+                raise ValueError("%s is on %s, the model on %s" % (name, t.device, self._device))
+            if not t.is_floating_point():
+                raise TypeError("%s must be a floating-point tensor (got %s)" % (name, t.dtype))
+        if q0.ndim not in (1, 2) or q0.shape[-1] != self._n_dofs:
+            raise ValueError("q0 must be [B, %d] or [%d], got %s" % (self._n_dofs, self._n_dofs, tuple(q0.shape)))
+        batch = q0.shape[:-1]
+        if target_pos.shape != batch + (3,):
+            raise ValueError("target_pos must be %s, got %s" % (tuple(batch + (3,)), tuple(target_pos.shape)))
+        if target_quat is not None and target_quat.shape != batch + (4,):
+            raise ValueError("target_quat must be %s, got %s" % (tuple(batch + (4,)), tuple(target_quat.shape)))
+        if link_name not in self._name_to_idx_map:
+            raise ValueError("unknown link %r" % (link_name,))
+        idx = self._name_to_idx_map[link_name]
+        if idx == 0:
+            raise ValueError("%r is the root link: it does not move" % (link_name,))
+        max_iterations = int(max_iterations)
+        if max_iterations < 0:
+            raise ValueError("max_iterations must be >= 0 (got %d)" % max_iterations)
+        damping, step_size, tol_pos, tol_rot = float(damping), float(step_size), float(tol_pos), float(tol_rot)
+        for name, v in (("damping", damping), ("step_size", step_size)):
+            if not (math.isfinite(v) and v > 0):
+                raise ValueError("%s must be finite and positive (got %r)" % (name, v))
+        for name, v in (("tol_pos", tol_pos), ("tol_rot", tol_rot)):
+            if not (math.isfinite(v) and v >= 0):
+                raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
+        single = q0.ndim == 1
+        if single:
+            q0, target_pos = q0.unsqueeze(0), target_pos.unsqueeze(0)
+            target_quat = target_quat.unsqueeze(0) if target_quat is not None else None
+        self._require_device()
+        with torch.no_grad():
+            dw = self._get_walk(("chain", idx), targets=[idx]) if self._learnable else self._chain_walk(idx)
+            ops_f = self._ops_f(dw).detach()
+            lower, upper = self._joint_bounds() if respect_joint_limits else (None, None)
+            q, err, iters = backend.inverse_kinematics(dw.program, ops_f, dw.ops_i, q0.detach(), target_pos.detach(),
+                                                       target_quat.detach() if target_quat is not None else None, max_iterations,
+                                                       damping, step_size, tol_pos, tol_rot, lower, upper, self._n_dofs,
+                                                       composed=bool(_composed))
+        pos_err = err[:, 0]
+        rot_err = err[:, 1] if target_quat is not None else None
+        # (the tolerances as the float32 values the kernel compared with)
+        converged = pos_err <= float(np.float32(tol_pos))
+        if rot_err is not None:
+            converged = converged & (rot_err <= float(np.float32(tol_rot)))
+        if single:
+            q, pos_err, iters, converged = q[0], pos_err[0], iters[0], converged[0]
+            rot_err = rot_err[0] if rot_err is not None else None
+        return InverseKinematicsResult(q=q, pos_err=pos_err, rot_err=rot_err, iterations=iters, converged=converged)
 
     def compute_forward_dynamics_old(self, q: torch.Tensor, qd: torch.Tensor, f: torch.Tensor,
                                      include_gravity: Optional[bool] = True, use_damping: Optional[bool] = True

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define DRM_ABI_VERSION 14
+#define DRM_ABI_VERSION 15
 
 /* ---- layout of one op (= one link) of a walk ---------------------------- */
 #define DRM_SPECIAL_KINDS 16 /* drm_walk.special[] (the kinds not named below are reserved and must be NULL): */
@@ -196,6 +196,9 @@ extern "C" {
 #define DRM_RNEA_DAMPING 2 /* tau += damping * qd             (robot_model.py:368-373)         */
 /* flags of drm_forward_dynamics_rollout (ABI 14), beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
 #define DRM_ROLLOUT_EXPLICIT_EULER 4 /* q += dt * qd_t, then qd += dt * qdd_t (default: semi-implicit Euler) */
+/* flags of drm_inverse_kinematics (ABI 15) */
+#define DRM_IK_POSITION_ONLY 1 /* target_pos only: a 3 x 3 system, rot_err written as 0 */
+#define DRM_IK_COMPOSED 2      /* force the composed path on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -425,6 +428,36 @@ int64_t drm_forward_dynamics_rollout_scratch_floats_aligned(const drm_walk *walk
 int drm_forward_dynamics_rollout(const drm_walk *walk, const float *q0, const float *qd0, const float *tau, int64_t B, int32_t T,
                                  float dt, int32_t flags, float *q_traj, float *qd_traj, float *qdd_traj, float *scratch,
                                  void *stream);
+
+/*
+ * ABI 15: batched inverse kinematics of one link by damped least squares, up to max_iters updates per row in one call.
+ * Row b starts at q0[b] and iteration i = 0, 1, .., max_iters evaluates at q_i:
+ *   p, c, Jp, Jw   = drm_fk_jacobian(q_i) of the walk's target (c an xyzw quaternion)
+ *   e_p = target_pos - p;  e_q = t (x) conj(c) with t = target_quat normalised (Hamilton product, negated if its w < 0);
+ *   with v = e_q.xyz, s = |v|, theta = 2 atan2(s, e_q.w):  e_R = v theta / s  (2 v when s == 0)
+ *   pos_err = |e_p|, rot_err = theta in [0, pi]
+ *   converged iff pos_err <= tol_pos && rot_err <= tol_rot.  A converged row, or every row at i == max_iters, writes q_i,
+ *   err = (pos_err, rot_err) and iters = i, and stops.  Otherwise, with J = [Jp; Jw] (6 x n) and e = [e_p; e_R]:
+ *   q_{i+1} = min(max(q_i + step * J^T (J J^T + damping^2 I)^-1 e, lower), upper)   (Cholesky, fp32)
+ * DRM_IK_POSITION_ONLY: J = Jp, e = e_p (3 x 3), convergence on pos_err alone, rot_err = 0; target_quat must be NULL then,
+ * and only then.  A row whose inputs are not finite never converges and returns non-finite values; it changes no other row.
+ *   q0 [B, n], target_pos [B, 3], target_quat [B, 4] or NULL  ->  q [B, n], err [B, 2], iters [B] (may be NULL)
+ *   lower, upper  [n] device arrays, both or neither (NULL: no clamp); +-inf entries leave a DoF free
+ * Full 64-row tiles of 7-DoF arm chains (DRM_WALK_ARM_CHAIN, capacity 8, target_perm 2, 16-byte aligned pointers) run ONE kernel
+ * that keeps q, the target and the Jacobian in registers across the iterations and leaves the loop when every row of the
+ * wavefront has stopped.  Every other robot, the ragged tail, misaligned pointers and DRM_IK_COMPOSED run max_iters + 1 rounds
+ * of drm_fk_jacobian into the scratch followed by a one-lane-per-row update kernel, without a host synchronisation.
+ *   scratch   drm_inverse_kinematics_scratch_floats_aligned(walk, B) floats when every pointer is 16-byte aligned (0 when the
+ *             fused kernel covers every row; scratch may then be NULL), drm_inverse_kinematics_scratch_floats(walk, B) floats
+ *             otherwise and with DRM_IK_COMPOSED (the composed path's FK + Jacobian, its input and a flag of every row)
+ * DRM_ERR_INVALID for bad arguments (max_iters < 0, damping or step not finite and > 0, a tolerance not finite and >= 0);
+ * B == 0 returns DRM_OK.  Asynchronous on `stream`.
+ */
+int64_t drm_inverse_kinematics_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_inverse_kinematics_scratch_floats_aligned(const drm_walk *walk, int64_t B); /* 16-byte aligned pointers (see Alignment) */
+int drm_inverse_kinematics(const drm_walk *walk, const float *q0, const float *target_pos, const float *target_quat, int64_t B,
+                           int32_t max_iters, float damping, float step, float tol_pos, float tol_rot, const float *lower,
+                           const float *upper, int32_t flags, float *q, float *err, int32_t *iters, float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on

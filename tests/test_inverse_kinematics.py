@@ -1,0 +1,519 @@
+"""Batched inverse kinematics by damped least squares (ABI 15, csrc/drm_ik.hip: every iteration of a solve in one call;
+DifferentiableRobotModel.compute_inverse_kinematics).
+
+CPU (not gpu): the host build (libdrm_cpu.so) against one update in numpy fp64 from the fp64 oracle's FK + Jacobian, against the
+Python loop of compute_fk_and_jacobian + a batched Cholesky solve that the feature replaces, calibrated convergence, invariants and
+the API.  GPU (-m gpu): the fused arm kernel and the composed path against the host build and against each other, ragged and
+misaligned launches, a full-size Panda solve and graph capture.
+
+The calibration setup (``seeded_problem``): q* uniform in the middle 80 % of each joint's range, target = FK(q*),
+q0 = clamp(q* + 0.1 N(0, 1)), damping 0.01, 32 iterations.
+"""
+import numpy as np
+import pytest
+import torch
+
+from differentiable_robot_model_amd import backend
+from helpers import ALL_ROBOTS, load_model
+from oracle import Oracle
+from test_forward_dynamics import tol_of
+
+# one link per shipped robot: the end effector, or a fingertip of a hand
+LINKS = {
+    "2link_robot": "endEffector",
+    "allegro_left": "link_3.0_tip",
+    "allegro_left_small_damping": "link_15.0_tip",
+    "fetch": "gripper_link",
+    "fetch_arm_no_gripper": "virtual_ee_link",
+    "fetch_arm_no_gripper_small_damping": "virtual_ee_link",
+    "iiwa7": "iiwa_link_ee",
+    "iiwa7_allegro": "link_3.0_tip",
+    "jaco": "j2n6s300_end_effector",
+    "jaco_clean": "j2n6s300_link_ee",
+    "panda": "panda_hand",
+    "panda_no_gripper": "panda_virtual_ee_link",
+    "trifinger_edu": "finger_tip_link_0",
+}
+# 7-DoF arm chains: the fused kernel's rows on the GPU
+FUSED = (("panda_no_gripper", "panda_virtual_ee_link"), ("iiwa7", "iiwa_link_ee"), ("fetch_arm_no_gripper", "virtual_ee_link"))
+
+
+def bounds(model):
+    lower, upper = model._joint_bounds()
+    return lower.cpu(), upper.cpu()
+
+
+def seeded_problem(model, link, B, seed=0, noise=0.1, pos_only=False):
+    """(q0, target_pos, target_quat or None, q*): the calibration setup of the module docstring, on the CPU (model: a CPU model)."""
+    lim = model.get_joint_limits()
+    lo = torch.tensor([l["lower"] for l in lim], dtype=torch.float32)
+    hi = torch.tensor([l["upper"] for l in lim], dtype=torch.float32)
+    free = lo >= hi
+    lo = torch.where(free, torch.full_like(lo, -np.pi), lo)
+    hi = torch.where(free, torch.full_like(hi, np.pi), hi)
+    g = torch.Generator().manual_seed(seed)
+    qs = lo + (hi - lo) * (0.1 + 0.8 * torch.rand(B, lo.shape[0], generator=g))
+    with torch.no_grad():
+        p, r = model.compute_forward_kinematics(qs, link)
+    blo, bhi = bounds(model)
+    q0 = torch.minimum(torch.maximum(qs + noise * torch.randn(qs.shape, generator=g), blo), bhi)
+    return q0, p.clone(), None if pos_only else r.clone(), qs
+
+
+def load(robot, device="cpu"):
+    return load_model(robot, device)
+
+
+def quat_mul(a, b):
+    ax, ay, az, aw = a.unbind(-1)
+    bx, by, bz, bw = b.unbind(-1)
+    return torch.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                        aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], -1)
+
+
+def errors(p, c, tp, tq):
+    """(e [B, 3 or 6], pos_err, rot_err or None) of the semantics (torch, any dtype)."""
+    e_p = tp - p
+    pos_err = e_p.norm(dim=-1)
+    if tq is None:
+        return e_p, pos_err, None
+    eq = quat_mul(tq, c * torch.tensor([-1.0, -1.0, -1.0, 1.0], dtype=c.dtype, device=c.device))
+    eq = torch.where(eq[..., 3:] < 0, -eq, eq)
+    v = eq[..., :3]
+    s = v.norm(dim=-1)
+    th = 2.0 * torch.atan2(s, eq[..., 3])
+    k = torch.where(s > 0, th / torch.where(s > 0, s, torch.ones_like(s)), torch.full_like(s, 2.0))
+    return torch.cat([e_p, v * k[..., None]], -1), pos_err, th
+
+
+def python_loop(model, link, q0, tp, tq, K, damping=0.01, step=1.0, tol_pos=1e-4, tol_rot=1e-3, lower=None, upper=None):
+    """The loop compute_inverse_kinematics replaces: compute_fk_and_jacobian, J J^T + lambda^2 I, a batched Cholesky solve, J^T y,
+    the clamps, fp32.  -> (q, pos_err, rot_err, iterations)"""
+    B, n = q0.shape
+    dev = q0.device
+    q = q0.clone()
+    tq = tq / tq.norm(dim=-1, keepdim=True) if tq is not None else None
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    iters = torch.full((B,), K, dtype=torch.int32, device=dev)
+    pe_out = torch.zeros(B, device=dev)
+    re_out = torch.zeros(B, device=dev)
+    m = 3 if tq is None else 6
+    eye = torch.eye(m, device=dev) * damping ** 2
+    with torch.no_grad():
+        for i in range(K + 1):
+            p, c, lin, ang = model.compute_fk_and_jacobian(q, link)
+            e, pos_err, rot_err = errors(p, c, tp, tq)
+            conv = pos_err <= tol_pos
+            if rot_err is not None:
+                conv = conv & (rot_err <= tol_rot)
+            stop = (conv | (i == K)) & ~done
+            pe_out = torch.where(stop, pos_err, pe_out)
+            if rot_err is not None:
+                re_out = torch.where(stop, rot_err, re_out)
+            iters = torch.where(stop, torch.full_like(iters, i), iters)
+            done = done | stop
+            if i == K:
+                break
+            J = lin if tq is None else torch.cat([lin, ang], 1)
+            L, _ = torch.linalg.cholesky_ex(J @ J.transpose(1, 2) + eye)
+            y = torch.cholesky_solve(e[..., None], L)
+            qn = q + step * (J.transpose(1, 2) @ y)[..., 0]
+            if lower is not None:
+                qn = torch.minimum(torch.maximum(qn, lower), upper)
+            q = torch.where(done[:, None], q, qn)
+    return q, pe_out, re_out, iters
+
+
+def check_close_rows(a, ref, tol):
+    """Two fp32 solves of the same rows (GPU / host, fused / composed): per row max |a - ref| / (1 + |ref|), at most `tol` on 99.9 %
+    of the rows and 5 tol on every row.  A row near a singular configuration amplifies the two builds' rounding differences by up
+    to cond(J J^T + damping^2 I) ~ 1e4 per update (Panda, 65 536 rows, K = 2: one row of 65 536 at 1.1e-3, 11 tol_of)."""
+    a = np.asarray(a, np.float64); ref = np.asarray(ref, np.float64)
+    r = (np.abs(a - ref) / (1.0 + np.abs(ref))).max(axis=-1)
+    assert np.quantile(r, 0.999) <= tol and r.max() <= 5 * tol, (np.quantile(r, 0.999), r.max())
+
+
+def rel(a, ref):
+    a = np.asarray(a, np.float64); ref = np.asarray(ref, np.float64)
+    return float((np.abs(a - ref) / (1.0 + np.abs(ref))).max())
+
+
+def fp64_step(model, link, q0, tp, tq, damping, lower, upper):
+    """q_1 of the semantics in numpy fp64 from the fp64 oracle's FK + Jacobian."""
+    q = np.asarray(q0, np.float64)
+    p, c, lin, ang = Oracle(model._spec).fk_jacobian(q, model._name_to_idx_map[link], np.float64)
+    tqt = None if tq is None else torch.from_numpy(np.asarray(tq, np.float64))
+    e, _, _ = errors(torch.from_numpy(p), torch.from_numpy(c), torch.from_numpy(np.asarray(tp, np.float64)),
+                     None if tqt is None else tqt / tqt.norm(dim=-1, keepdim=True))
+    e = e.numpy()
+    J = lin if tq is None else np.concatenate([lin, ang], 1)
+    A = J @ J.transpose(0, 2, 1) + damping ** 2 * np.eye(J.shape[1])
+    dq = (J.transpose(0, 2, 1) @ np.linalg.solve(A, e[..., None]))[..., 0]
+    q1 = q + dq
+    if lower is not None:
+        q1 = np.minimum(np.maximum(q1, np.asarray(lower, np.float64)), np.asarray(upper, np.float64))
+    return q1
+
+
+# ----------------------------------------------------------------------------------------------------------------------- CPU
+
+
+def test_every_shipped_robot_has_a_link():
+    assert sorted(LINKS) == sorted(ALL_ROBOTS)
+
+
+@pytest.mark.parametrize("robot", ALL_ROBOTS)
+@pytest.mark.parametrize("pos_only", [False, True])
+@pytest.mark.parametrize("limits", [True, False])
+def test_one_step_against_fp64(robot, pos_only, limits):
+    """K = 1 with tolerances 0: every row takes exactly one update.  q_1 against the same update in fp64 from the oracle, relative
+    to 1 + |q|, within 4 tol_of(robot).  Host build, 256 rows: at most 1.5e-4 (Panda, 6D; 1.5 tol_of), 1.2e-4 on the Fetch arm and
+    6e-5 on the iiwa at 6D, below 2e-5 in every position-only case: the fp32 Cholesky of J J^T + 1e-4 I loses up to ~1e4 ulp on rows
+    near a singular configuration."""
+    m = load(robot)
+    link = LINKS[robot]
+    q0, tp, tq, _ = seeded_problem(m, link, 256, seed=1, pos_only=pos_only)
+    res = m.compute_inverse_kinematics(q0, link, tp, tq, max_iterations=1, tol_pos=0.0, tol_rot=0.0, respect_joint_limits=limits)
+    assert (res.iterations == 1).all()
+    lower, upper = bounds(m) if limits else (None, None)
+    want = fp64_step(m, link, q0, tp, tq, 0.01, lower, upper)
+    assert rel(res.q, want) <= 4 * tol_of(robot)
+    if limits:
+        assert ((res.q >= lower) & (res.q <= upper)).all()
+
+
+@pytest.mark.parametrize("robot,link,pos_only", [(r, l, False) for r, l in FUSED] +
+                         [("allegro_left", "link_3.0_tip", True), ("jaco", "j2n6s300_end_effector", False),
+                          ("fetch", "gripper_link", False), ("trifinger_edu", "finger_tip_link_0", True)])
+def test_against_python_loop(robot, link, pos_only):
+    """K = 8 against the Python loop it replaces (fp32): the same iteration count on >= 99 % of the rows and, on those, q within
+    5e-4 relative to 1 + |q|.  Host build, 512 rows: 100 % equal counts on all seven cases, q within 7.2e-5 (iiwa) at most; the two
+    solves round differently, so a row that ends near a tolerance could stop one iteration apart."""
+    m = load(robot)
+    q0, tp, tq, _ = seeded_problem(m, link, 512, seed=2, pos_only=pos_only)
+    lower, upper = bounds(m)
+    res = m.compute_inverse_kinematics(q0, link, tp, tq, max_iterations=8)
+    q, pe, re, it = python_loop(m, link, q0, tp, tq, 8, lower=lower, upper=upper)
+    same = res.iterations == it
+    assert same.float().mean() >= 0.99
+    assert rel(res.q[same], q[same]) <= 5e-4
+
+
+# calibrated on the host build, seeded_problem(seed=3), 2 048 rows, defaults: converged fraction (floor = value - margin)
+CONVERGENCE = {
+    ("panda_no_gripper", "panda_virtual_ee_link", False): 0.99,
+    ("iiwa7", "iiwa_link_ee", False): 0.99,
+    ("fetch_arm_no_gripper", "virtual_ee_link", False): 0.99,
+    ("allegro_left", "link_3.0_tip", True): 0.995,
+}
+
+
+@pytest.mark.parametrize("robot,link,pos_only", list(CONVERGENCE))
+def test_convergence_calibrated(robot, link, pos_only):
+    """The converged fraction of the calibration setup at the defaults.  Host build, 2 048 rows: Panda 99.56 % (median 3
+    iterations, 99th percentile 19, mean 3.5), iiwa 99.61 % (3, 14, 3.5), Fetch arm 99.61 % (3, 13, 3.3), Allegro fingertip
+    (position only) 100 % (2, 7, 2.6).  Every converged
+    row's reported errors agree with compute_forward_kinematics(res.q) to 1e-6 and every bounded DoF is within its limits."""
+    m = load(robot)
+    q0, tp, tq, _ = seeded_problem(m, link, 2048, seed=3, pos_only=pos_only)
+    res = m.compute_inverse_kinematics(q0, link, tp, tq)
+    assert res.converged.float().mean() >= CONVERGENCE[(robot, link, pos_only)]
+    check_result(m, link, res, tp, tq, torch.device("cpu"))
+
+
+def check_result(m, link, res, tp, tq, dev, atol=1e-6):
+    """converged rows: reported errors = FK of the result recomputed, within the tolerances; bounded DoFs within the limits"""
+    c = res.converged
+    with torch.no_grad():
+        p, r = m.compute_forward_kinematics(res.q, link)
+    _, pe, re = errors(p, r, tp.to(dev), None if tq is None else (tq / tq.norm(dim=-1, keepdim=True)).to(dev))
+    assert torch.allclose(res.pos_err[c], pe[c], atol=atol, rtol=0)
+    assert (res.pos_err[c] <= 1e-4).all()
+    if tq is None:
+        assert res.rot_err is None
+    else:
+        assert torch.allclose(res.rot_err[c], re[c], atol=atol, rtol=0)
+        assert (res.rot_err[c] <= 1e-3).all()
+    lower, upper = m._joint_bounds()
+    assert ((res.q >= lower) | torch.isinf(lower)).all() and ((res.q <= upper) | torch.isinf(upper)).all()
+
+
+def test_start_on_target_returns_q0():
+    m = load("panda_no_gripper")
+    q0, _, _, _ = seeded_problem(m, "panda_virtual_ee_link", 64, seed=4)
+    p, r = m.compute_forward_kinematics(q0, "panda_virtual_ee_link")
+    res = m.compute_inverse_kinematics(q0, "panda_virtual_ee_link", p, r)
+    assert torch.equal(res.q, q0) and (res.iterations == 0).all() and res.converged.all()
+
+
+def test_more_iterations_keep_converged_rows():
+    m = load("iiwa7")
+    q0, tp, tq, _ = seeded_problem(m, "iiwa_link_ee", 512, seed=5, noise=0.3)
+    a = m.compute_inverse_kinematics(q0, "iiwa_link_ee", tp, tq, max_iterations=4)
+    b = m.compute_inverse_kinematics(q0, "iiwa_link_ee", tp, tq, max_iterations=16)
+    c = a.converged
+    assert 0 < c.sum() < len(c)
+    assert torch.equal(a.q[c], b.q[c]) and torch.equal(a.iterations[c], b.iterations[c])
+    assert torch.equal(a.pos_err[c], b.pos_err[c]) and torch.equal(a.rot_err[c], b.rot_err[c])
+
+
+def check_alone_vs_batch(robot, link, dev, exact=(0, 100, 256)):
+    """A row solved alone = the same row inside a batch of 257, bit for bit for the rows in `exact`.  (On the GPU a row alone and
+    the ragged tail row 256 go through the same kernels; the rows of the batch's full tiles take the fused kernel (7-DoF arms) or
+    drm_fk_jacobian's straight-line chain kernel, a row alone the loop kernel: equal within rounding only.)"""
+    m = load(robot, dev)
+    q0, tp, tq, _ = seeded_problem(load(robot), link, 257, seed=6)
+    q0, tp, tq = q0.to(dev), tp.to(dev), tq.to(dev)
+    full = m.compute_inverse_kinematics(q0, link, tp, tq)
+    for b in (0, 100, 256):
+        one = m.compute_inverse_kinematics(q0[b], link, tp[b], tq[b])
+        if b in exact:
+            assert torch.equal(one.q, full.q[b]) and one.iterations == full.iterations[b]
+        else:
+            check_close_rows(one.q[None].cpu(), full.q[b][None].cpu(), 4 * tol_of(robot))
+
+
+def test_row_alone_equals_row_in_batch():
+    check_alone_vs_batch("fetch_arm_no_gripper", "virtual_ee_link", "cpu")
+
+
+def check_nan_row(robot, link, dev, B=130):
+    m = load(robot, dev)
+    q0, tp, tq, _ = seeded_problem(load(robot), link, B, seed=7)
+    q0, tp, tq = q0.to(dev), tp.to(dev), tq.to(dev)
+    ref = m.compute_inverse_kinematics(q0, link, tp, tq)
+    tp2 = tp.clone()
+    tp2[5, 1] = float("nan")
+    res = m.compute_inverse_kinematics(q0, link, tp2, tq)
+    assert not res.converged[5] and not torch.isfinite(res.pos_err[5])
+    keep = torch.arange(B, device=dev) != 5
+    assert torch.equal(res.q[keep], ref.q[keep]) and torch.equal(res.iterations[keep], ref.iterations[keep])
+    assert torch.equal(res.pos_err[keep], ref.pos_err[keep])
+
+
+def test_nan_target_row_is_isolated():
+    check_nan_row("panda_no_gripper", "panda_virtual_ee_link", "cpu")
+
+
+def test_no_autograd_history():
+    m = load("panda_no_gripper")
+    q0, tp, tq, _ = seeded_problem(m, "panda_virtual_ee_link", 8, seed=8)
+    q0.requires_grad_(True)
+    tp.requires_grad_(True)
+    res = m.compute_inverse_kinematics(q0, "panda_virtual_ee_link", tp, tq)
+    for t in (res.q, res.pos_err, res.rot_err, res.iterations, res.converged):
+        assert not t.requires_grad and t.grad_fn is None
+
+
+def learnable_iiwa(device="cpu"):
+    from differentiable_robot_model_amd.rigid_body_params import UnconstrainedTensor
+    m = load("iiwa7", device)
+    m.make_link_param_learnable("iiwa_link_3", "trans", UnconstrainedTensor(1, 3, init_tensor=torch.tensor([[0.01, -0.02, 0.03]])))
+    m.make_link_param_learnable("iiwa_link_3", "rot_angles", UnconstrainedTensor(1, 3, init_tensor=torch.tensor([[0.05, 0.0, -0.04]])))
+    return m
+
+
+def test_learnable_model_matches_python_loop():
+    """A learnable model solves against its current (perturbed) parameters, like the Python loop on the same model."""
+    m = learnable_iiwa()
+    q0, tp, tq, _ = seeded_problem(m, "iiwa_link_ee", 256, seed=9)          # (targets reachable by the perturbed model)
+    lower, upper = bounds(m)
+    res = m.compute_inverse_kinematics(q0, "iiwa_link_ee", tp, tq, max_iterations=8)
+    q, pe, re, it = python_loop(m, "iiwa_link_ee", q0, tp, tq, 8, lower=lower, upper=upper)
+    same = res.iterations == it
+    assert same.float().mean() >= 0.99
+    assert rel(res.q[same], q[same]) <= 5e-4
+    const = load("iiwa7").compute_inverse_kinematics(q0, "iiwa_link_ee", tp, tq, max_iterations=8)
+    assert not torch.equal(const.q, res.q)      # (the perturbation matters)
+
+
+def test_unbatched_and_position_only():
+    m = load("panda_no_gripper")
+    q0, tp, tq, _ = seeded_problem(m, "panda_virtual_ee_link", 4, seed=10)
+    one = m.compute_inverse_kinematics(q0[1], "panda_virtual_ee_link", tp[1], tq[1])
+    assert one.q.shape == (7,) and one.pos_err.shape == () and one.rot_err.shape == () and one.iterations.shape == ()
+    assert one.iterations.dtype == torch.int32 and one.converged.dtype == torch.bool
+    po = m.compute_inverse_kinematics(q0, "panda_virtual_ee_link", tp)
+    assert po.rot_err is None and po.q.shape == (4, 7) and po.pos_err.shape == (4,)
+    assert po.converged.all()
+
+
+def test_bad_arguments():
+    m = load("panda_no_gripper")
+    q0, tp, tq, _ = seeded_problem(m, "panda_virtual_ee_link", 4, seed=11)
+    link = "panda_virtual_ee_link"
+    with pytest.raises(ValueError):
+        m.compute_inverse_kinematics(q0[:, :6], link, tp, tq)
+    with pytest.raises(ValueError):
+        m.compute_inverse_kinematics(q0, link, tp[:3], tq)
+    with pytest.raises(ValueError):
+        m.compute_inverse_kinematics(q0, link, tp, tq[:, :3])
+    with pytest.raises(ValueError):
+        m.compute_inverse_kinematics(q0, "no_such_link", tp, tq)
+    with pytest.raises(TypeError):
+        m.compute_inverse_kinematics(q0.to(torch.int64), link, tp, tq)
+    with pytest.raises(TypeError):
+        m.compute_inverse_kinematics(q0.numpy(), link, tp, tq)
+    for kw in (dict(max_iterations=-1), dict(damping=0.0), dict(damping=float("nan")), dict(step_size=-1.0),
+               dict(step_size=float("inf")), dict(tol_pos=-1e-4), dict(tol_rot=float("inf"))):
+        with pytest.raises(ValueError):
+            m.compute_inverse_kinematics(q0, link, tp, tq, **kw)
+    # float64 inputs are taken (as float32), and K = 0 only measures the errors
+    res = m.compute_inverse_kinematics(q0.double(), link, tp.double(), tq.double(), max_iterations=0)
+    assert (res.iterations == 0).all() and torch.equal(res.q, q0)
+
+
+def test_device_mismatch_is_refused():
+    m = load("panda_no_gripper")
+    q0, tp, tq, _ = seeded_problem(m, "panda_virtual_ee_link", 4, seed=12)
+    with pytest.raises(ValueError):
+        m.compute_inverse_kinematics(q0, "panda_virtual_ee_link", tp.to("meta"), tq)
+
+
+def test_continuous_joints_are_free():
+    """Fetch's continuous joints parse as lower = upper = 0: free, -inf / +inf."""
+    m = load("fetch")
+    lower, upper = m._joint_bounds()
+    lim = m.get_joint_limits()
+    for d, l in enumerate(lim):
+        if not l["lower"] < l["upper"]:
+            assert lower[d] == -np.inf and upper[d] == np.inf
+        else:
+            assert lower[d] == np.float32(l["lower"]) and upper[d] == np.float32(l["upper"])
+    assert torch.isinf(lower).any()
+
+
+def test_abi_entry_points():
+    lib = backend.load_library(kind="cpu")
+    assert lib.drm_abi_version() == 15
+    m = load("panda_no_gripper")
+    dw = m._chain_walk(m._name_to_idx_map["panda_virtual_ee_link"])
+    walk = backend._walk_struct(dw.program, m._ops_f(dw), dw.ops_i, 7)
+    import ctypes
+    assert lib.drm_inverse_kinematics_scratch_floats(ctypes.byref(walk), 100) == 0
+    q = torch.zeros(1, 7)
+    out = torch.empty(1, 7)
+    err = torch.empty(1, 2)
+    # target_quat given together with DRM_IK_POSITION_ONLY: refused
+    rc = lib.drm_inverse_kinematics(ctypes.byref(walk), q.data_ptr(), torch.zeros(1, 3).data_ptr(), torch.zeros(1, 4).data_ptr(), 1, 4,
+                                    0.01, 1.0, 0.0, 0.0, None, None, backend.IK_POSITION_ONLY, out.data_ptr(), err.data_ptr(), None,
+                                    None, None)
+    assert rc == -1
+    rc = lib.drm_inverse_kinematics(ctypes.byref(walk), q.data_ptr(), torch.zeros(1, 3).data_ptr(), None, 0, 4, 0.01, 1.0, 0.0, 0.0,
+                                    None, None, backend.IK_POSITION_ONLY, out.data_ptr(), err.data_ptr(), None, None, None)
+    assert rc == 0
+
+
+# ----------------------------------------------------------------------------------------------------------------------- GPU
+
+
+def gpu_and_host(robot, link, B, seed, K, pos_only=False, composed=False, **kw):
+    cpu, gpu = load(robot), load(robot, "cuda:0")
+    q0, tp, tq, _ = seeded_problem(cpu, link, B, seed=seed, pos_only=pos_only)
+    want = cpu.compute_inverse_kinematics(q0, link, tp, tq, max_iterations=K, **kw)
+    got = gpu.compute_inverse_kinematics(q0.cuda(), link, tp.cuda(), None if tq is None else tq.cuda(), max_iterations=K,
+                                         _composed=composed, **kw)
+    return cpu, gpu, (q0, tp, tq), want, got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot,link", FUSED)
+@pytest.mark.parametrize("B", [64, 4096, 65536])
+def test_gpu_fused_against_host(robot, link, B):
+    for K in (1, 2):
+        _, _, _, want, got = gpu_and_host(robot, link, B, B + K, K, tol_pos=0.0, tol_rot=0.0)
+        check_close_rows(got.q.cpu(), want.q, 4 * tol_of(robot))
+    _, gpu, (q0, tp, tq), want, got = gpu_and_host(robot, link, B, B, 32)
+    assert abs(got.converged.float().mean().item() - want.converged.float().mean().item()) <= 0.005 + 2.0 / B
+    check_result(gpu, link, got, tp, tq, torch.device("cuda:0"), atol=2e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot,link", FUSED)
+def test_gpu_fused_against_composed(robot, link):
+    gpu = load(robot, "cuda:0")
+    q0, tp, tq, _ = seeded_problem(load(robot), link, 4096, seed=21)
+    q0, tp, tq = q0.cuda(), tp.cuda(), tq.cuda()
+    for K in (1, 32):
+        kw = dict(max_iterations=K, tol_pos=0.0, tol_rot=0.0) if K == 1 else dict(max_iterations=K)
+        a = gpu.compute_inverse_kinematics(q0, link, tp, tq, **kw)
+        b = gpu.compute_inverse_kinematics(q0, link, tp, tq, _composed=True, **kw)
+        if K == 1:
+            check_close_rows(a.q.cpu(), b.q.cpu(), 4 * tol_of(robot))
+        else:
+            assert abs(a.converged.float().mean().item() - b.converged.float().mean().item()) <= 0.005
+            assert abs(a.iterations.float().mean().item() - b.iterations.float().mean().item()) <= 0.1
+            check_result(gpu, link, b, tp, tq, torch.device("cuda:0"), atol=2e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot,link,pos_only", [("fetch", "gripper_link", False), ("jaco", "j2n6s300_end_effector", False),
+                                                 ("allegro_left", "link_3.0_tip", True), ("trifinger_edu", "finger_tip_link_0", False),
+                                                 ("2link_robot", "endEffector", True)])
+def test_gpu_composed_against_host(robot, link, pos_only):
+    for B in (1, 63, 64, 65, 257):
+        for K in (1, 16):
+            kw = dict(tol_pos=0.0, tol_rot=0.0) if K == 1 else {}
+            _, _, _, want, got = gpu_and_host(robot, link, B, B, K, pos_only=pos_only, **kw)
+            if K == 1:
+                check_close_rows(got.q.cpu(), want.q, 4 * tol_of(robot))
+            else:
+                same = got.iterations.cpu() == want.iterations
+                assert same.float().mean() >= 0.95
+                assert rel(got.q.cpu()[same], want.q[same]) <= 1e-3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot,link", [("panda_no_gripper", "panda_virtual_ee_link"), ("fetch", "gripper_link")])
+def test_gpu_ragged_and_misaligned(robot, link):
+    gpu = load(robot, "cuda:0")
+    q0, tp, tq, _ = seeded_problem(load(robot), link, 4096 + 37, seed=22)
+    q0, tp, tq = q0.cuda(), tp.cuda(), tq.cuda()
+    full = gpu.compute_inverse_kinematics(q0, link, tp, tq)
+    head = gpu.compute_inverse_kinematics(q0[:4096], link, tp[:4096], tq[:4096])
+    tail = gpu.compute_inverse_kinematics(q0[4096:].clone(), link, tp[4096:].clone(), tq[4096:].clone())
+    assert torch.equal(full.q, torch.cat([head.q, tail.q])) and torch.equal(full.iterations, torch.cat([head.iterations, tail.iterations]))
+    # an offset view (rows 1 ..): not 16-byte aligned
+    view = gpu.compute_inverse_kinematics(q0[1:65], link, tp[1:65], tq[1:65])
+    alone = gpu.compute_inverse_kinematics(q0[1:65].clone(), link, tp[1:65].clone(), tq[1:65].clone())
+    assert torch.equal(view.q, alone.q) and torch.equal(view.iterations, alone.iterations)
+
+
+@pytest.mark.gpu
+def test_gpu_full_size_panda():
+    link = "panda_virtual_ee_link"
+    gpu = load("panda_no_gripper", "cuda:0")
+    q0, tp, tq, _ = seeded_problem(load("panda_no_gripper"), link, 65536, seed=23)
+    tp, tq = tp.cuda(), tq.cuda()
+    res = gpu.compute_inverse_kinematics(q0.cuda(), link, tp, tq)
+    assert res.converged.float().mean() >= 0.99
+    check_result(gpu, link, res, tp, tq, torch.device("cuda:0"), atol=2e-6)
+
+
+@pytest.mark.gpu
+def test_gpu_invariants():
+    check_alone_vs_batch("panda_no_gripper", "panda_virtual_ee_link", "cuda:0", exact=(256,))
+    check_alone_vs_batch("fetch", "gripper_link", "cuda:0", exact=(256,))
+    check_nan_row("panda_no_gripper", "panda_virtual_ee_link", "cuda:0", B=4096)      # (the fused kernel)
+    check_nan_row("fetch", "gripper_link", "cuda:0", B=4096)                          # (the composed path)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot,link", [("panda_no_gripper", "panda_virtual_ee_link"), ("jaco", "j2n6s300_end_effector")])
+def test_gpu_graph_capture_bit_equal(robot, link):
+    m = load(robot, "cuda:0")
+    q0, tp, tq, _ = seeded_problem(load(robot), link, 256 + 5, seed=24)
+    q0, tp, tq = q0.cuda(), tp.cuda(), tq.cuda()
+    eager = m.compute_inverse_kinematics(q0, link, tp, tq, max_iterations=8)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        m.compute_inverse_kinematics(q0, link, tp, tq, max_iterations=8)          # warm-up on the capture stream
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        captured = m.compute_inverse_kinematics(q0, link, tp, tq, max_iterations=8)
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(captured.q, eager.q) and torch.equal(captured.iterations, eager.iterations)
+    assert torch.equal(captured.pos_err, eager.pos_err) and torch.equal(captured.converged, eager.converged)
