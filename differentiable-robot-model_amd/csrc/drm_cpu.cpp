@@ -306,6 +306,10 @@ int drm_inverse_kinematics(const drm_walk *w, const float *q0, const float *targ
             for (int i = 0;; ++i) {
                 float p[3], c[4], pos_err, rot_err;
                 jac_loop(w, qr, 1, p, c, lin.data(), ang.data());
+                // as the device kernels: a row whose q is not finite in ANY DoF, one off the link's chain included, gets a NaN error
+                bool ok = true;
+                for (int k = 0; k < n; ++k) ok = ok && std::isfinite(qr[k]);
+                if (!ok) p[0] = NAN;
                 if (drm::ik_iteration(J, n, p, c, target_pos + b * 3, tq, pos_only, o, i == max_iters, qf, lower, upper, pos_err, rot_err)) {
                     err[b * 2] = pos_err;
                     err[b * 2 + 1] = rot_err;

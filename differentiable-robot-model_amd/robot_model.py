@@ -1480,7 +1480,8 @@ class DifferentiableRobotModel(torch.nn.Module):
         otherwise q_{i+1} = clamp(q_i + step_size * J^T (J J^T + damping^2 I)^-1 e) (J = [lin_jac; ang_jac], 6 x n; lin_jac alone,
         3 x n, in position-only mode) between the joint limits of get_joint_limits() (respect_joint_limits; a continuous joint
         is free).  One kernel launch per solve for 7-DoF arms (csrc/drm_ik.hip), two per iteration for every other robot, never a
-        host synchronisation.  Unbatched q0 [n] with target_pos [3] give unbatched results.
+        host synchronisation.  Unbatched q0 [n] with target_pos [3] give unbatched results.  A row whose q0 (in any DoF, one the
+        link does not depend on included), target_pos or target_quat is not finite never reports convergence and changes no other row.
 
         The results carry NO autograd history, even when the inputs or the learnable link parameters require grad: the solve is
         not differentiable here.  A model with learnable links solves against their current values.  (``_composed``: every row takes

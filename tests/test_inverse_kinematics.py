@@ -138,10 +138,11 @@ def rel(a, ref):
     return float((np.abs(a - ref) / (1.0 + np.abs(ref))).max())
 
 
-def fp64_step(model, link, q0, tp, tq, damping, lower, upper):
-    """q_1 of the semantics in numpy fp64 from the fp64 oracle's FK + Jacobian."""
+def fp64_step(model, link, q0, tp, tq, damping, lower, upper, step_size=1.0, spec=None, unclamped=False):
+    """q_1 of the semantics in numpy fp64 from the fp64 oracle's FK + Jacobian (spec: the robot description to use instead of the
+    model's own, for a model with learnable links; unclamped: also return q_1 before the clamp)."""
     q = np.asarray(q0, np.float64)
-    p, c, lin, ang = Oracle(model._spec).fk_jacobian(q, model._name_to_idx_map[link], np.float64)
+    p, c, lin, ang = Oracle(spec if spec is not None else model._spec).fk_jacobian(q, model._name_to_idx_map[link], np.float64)
     tqt = None if tq is None else torch.from_numpy(np.asarray(tq, np.float64))
     e, _, _ = errors(torch.from_numpy(p), torch.from_numpy(c), torch.from_numpy(np.asarray(tp, np.float64)),
                      None if tqt is None else tqt / tqt.norm(dim=-1, keepdim=True))
@@ -149,10 +150,10 @@ def fp64_step(model, link, q0, tp, tq, damping, lower, upper):
     J = lin if tq is None else np.concatenate([lin, ang], 1)
     A = J @ J.transpose(0, 2, 1) + damping ** 2 * np.eye(J.shape[1])
     dq = (J.transpose(0, 2, 1) @ np.linalg.solve(A, e[..., None]))[..., 0]
-    q1 = q + dq
+    u = q1 = q + step_size * dq
     if lower is not None:
         q1 = np.minimum(np.maximum(q1, np.asarray(lower, np.float64)), np.asarray(upper, np.float64))
-    return q1
+    return (q1, u) if unclamped else q1
 
 
 # ----------------------------------------------------------------------------------------------------------------------- CPU
