@@ -5,6 +5,7 @@
 // 1 608 -> 1 465 VALU per wave here, 50.5 -> 46.6 us at 2^20 (the FK + Jacobian kernel, whose pairs are laid out by hand,
 // is 6 % shorter WITH it and stays in drm_arm_kernels.hip).
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_arm_stream.hpp"
 
@@ -267,11 +268,11 @@ int64_t launch_rnea_fingers(const drm_walk *w, const float *q, const float *qd, 
 #ifdef DRM_NO_FINGERS_KERNEL
     return 0;
 #else
-    if (!(w->shape & DRM_WALK_FINGERS) || B < TILE2 || B / TILE2 >= 0x7fffffffLL || (((uintptr_t)w->ops_f) & 15u) != 0) return 0;
-    const int K = DRM_WALK_AH_K(w->shape), L = DRM_WALK_AH_L(w->shape), n = w->n_dofs;
-    if (K * L != w->n_ops || n != w->n_ops || K < 2 || K > 4 || L < 2 || L > 4) return 0;
-    const int n2 = (int)(B / TILE2);
-    const int vec = (n % 4 == 0) && ((((uintptr_t)q | (uintptr_t)qd | (uintptr_t)qdd | (uintptr_t)tau) & 15u) == 0);
+    if (!(w->shape & DRM_WALK_FINGERS) || !full_tiles_fit(B, TILE2) || !table_aligned(w)) return 0;
+    int K, L;
+    if (!fingers_shape(w, K, L)) return 0;
+    const int n = w->n_dofs, n2 = (int)(B / TILE2);
+    const int vec = (n % 4 == 0) && aligned16(q, qd, qdd, tau);
 #define X(l)                                                                                                                     \
     if (L == l) hipLaunchKernelGGL((rnea_fingers2_kernel<l>), dim3((unsigned)n2), dim3(WAVE * K), 0, s, w->ops_f, q, qd, qdd, n, flags, tau, vec);
     X(2) X(3) X(4)

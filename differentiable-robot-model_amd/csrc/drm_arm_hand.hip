@@ -13,6 +13,7 @@
 // count.  Full 64-row tiles only; a ragged tail goes through the loop-structured kernels.
 // Build flags as drm_arm_dynamics.hip (kernel-argument preload, no SLP vectoriser).
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree.hpp"
 #include "drm_tree_dev.hpp"
@@ -414,7 +415,7 @@ bool arm_hand_compiled(const drm_walk *w) {
 int64_t launch_rnea_arm_hand(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int flags, float *tau,
                              hipStream_t s) {
     int P, K, L;
-    if (!arm_hand_compiled(w) || !shape_of(w, P, K, L) || B < WAVE || B / WAVE >= 0x7fffffffLL || (((uintptr_t)w->ops_f) & 15u) != 0)
+    if (!arm_hand_compiled(w) || !shape_of(w, P, K, L) || !full_tiles_fit(B) || !table_aligned(w))
         return 0;
     const uint32_t al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(tau, AL_TAU) | (qdd ? al16(qdd, AL_QDD) : AL_QDD);
     if (al != (AL_Q | AL_QD | AL_QDD | AL_TAU)) return 0;
@@ -437,7 +438,7 @@ int64_t launch_forward_dynamics_arm_hand(const drm_walk *w, const float *q, cons
     return 0;
 #else
     int P, K, L;
-    if (!arm_hand_compiled(w) || !shape_of(w, P, K, L) || B < WAVE || B / WAVE >= 0x7fffffffLL || (((uintptr_t)w->ops_f) & 15u) != 0)
+    if (!arm_hand_compiled(w) || !shape_of(w, P, K, L) || !full_tiles_fit(B) || !table_aligned(w))
         return 0;
     const uint32_t al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(f, AL_QDD) | al16(qdd, AL_TAU);
     if (al != (AL_Q | AL_QD | AL_QDD | AL_TAU)) return 0;
@@ -495,8 +496,7 @@ int64_t launch_crba_arm_hand(const drm_walk *w, const float *q, int64_t B, float
     return 0;
 #else
     int P, K, L;
-    if (!crba_arm_hand_applies(w) || !shape_of(w, P, K, L) || B < WAVE || B / WAVE >= 0x7fffffffLL ||
-        (((uintptr_t)w->ops_f | (uintptr_t)q | (uintptr_t)H) & 15u) != 0)
+    if (!crba_arm_hand_applies(w) || !shape_of(w, P, K, L) || !full_tiles_fit(B) || !aligned16(w->ops_f, q, H))
         return 0;
     const int n_tiles = (int)(B / WAVE);
     const bool nt = stream_past_llc((int64_t)n_tiles * WAVE * w->n_dofs * w->n_dofs * 4);
@@ -542,7 +542,7 @@ int64_t launch_rnea_backward_arm_hand(const drm_walk *w, const float *q, const f
     int P, K, L;
     const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)qd | (uintptr_t)qdd | (uintptr_t)gtau | (uintptr_t)gq | (uintptr_t)gqd |
                            (uintptr_t)gqdd | (uintptr_t)w->ops_f;
-    if (!arm_hand_compiled(w) || !shape_of(w, P, K, L) || K > 4 || B < WAVE || B / WAVE >= 0x7fffffffLL || (ptrs & 15u) != 0) return 0;
+    if (!arm_hand_compiled(w) || !shape_of(w, P, K, L) || K > 4 || !full_tiles_fit(B) || (ptrs & 15u) != 0) return 0;
     const int n_tiles = (int)(B / WAVE);
     // as many one-wavefront blocks as the device holds at once (a grid of 2 048 on a chip that holds 1 792 runs two rounds)
     int resident = 0, rc = DRM_ERR_UNSUPPORTED;

@@ -4,6 +4,7 @@
 // registers and spill nothing, whereas the big table-driven kernels gain nothing from it and one of them faulted with it.
 // The C ABI entry points (drm_fk_jacobian.hip, drm_fk.hip, drm_rnea.hip) call the launch_* functions below.
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 
 namespace drm {
@@ -148,9 +149,7 @@ int64_t launch_fk_arm(const drm_walk *w, const float *q, int64_t B, float *pos, 
     return 0;
 #else
     const uint32_t align = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
-    if (!((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && w->n_dofs == 7 && w->target_perm == 2 &&
-          align == (AL_Q | AL_POS | AL_QUAT) && (((uintptr_t)w->ops_f) & 15u) == 0 && B >= WAVE &&
-          B / WAVE < 0x7fffffffLL))
+    if (!(arm7_walk(w) && w->target_perm == 2 && align == (AL_Q | AL_POS | AL_QUAT) && table_aligned(w) && full_tiles_fit(B)))
         return 0;
     const int n_tiles = (int)(B / WAVE);
     hipLaunchKernelGGL((fk_jacobian_arm_kernel<8, 7, false, 1, false>), dim3((unsigned)n_tiles), dim3(WAVE), 0, s, w->ops_f, q,

@@ -20,6 +20,7 @@
 //                                   wavefront t of a block walks chain t, the [64, 3T] / [64, 4T] tiles are assembled in
 //                                   LDS and leave as linear 16-byte stores
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 
 namespace drm {
@@ -388,7 +389,7 @@ __global__ void __launch_bounds__(WAVE * 4)
 static bool chain_ok(const drm_walk *w) {
     return (w->shape & DRM_WALK_SERIAL_CHAIN) && (w->shape & DRM_WALK_CHAIN_DOFS) && (w->capacity == 4 || w->capacity == 8 || w->capacity == 12 || w->capacity == 16) &&
            w->n_ops >= 1 &&
-           w->n_slots == 0 && (((uintptr_t)w->ops_f) & 15u) == 0 && w->target_perm >= 0 && w->target_perm <= 5;
+           w->n_slots == 0 && table_aligned(w) && w->target_perm >= 0 && w->target_perm <= 5;
 }
 
 template <int CAP, int USED, bool JAC>
@@ -419,7 +420,7 @@ int64_t launch_chain_fk_jacobian(const drm_walk *w, const float *q, int64_t B, f
     return 0;
 #else
     const uint32_t al = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT) | al16(lin, AL_LIN) | al16(ang, AL_ANG);
-    if (!chain_ok(w) || !pos || !quat || al != (AL_Q | AL_POS | AL_QUAT | AL_LIN | AL_ANG) || B < WAVE || B / WAVE >= 0x7fffffffLL ||
+    if (!chain_ok(w) || !pos || !quat || al != (AL_Q | AL_POS | AL_QUAT | AL_LIN | AL_ANG) || !full_tiles_fit(B) ||
         w->n_dofs > 32)
         return 0;
     const int n_tiles = (int)(B / WAVE);
@@ -436,7 +437,7 @@ int64_t launch_chain_fk(const drm_walk *w, const float *q, int64_t B, float *pos
     return 0;
 #else
     const uint32_t al = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
-    if (!chain_ok(w) || al != (AL_Q | AL_POS | AL_QUAT) || B < WAVE || B / WAVE >= 0x7fffffffLL) return 0;
+    if (!chain_ok(w) || al != (AL_Q | AL_POS | AL_QUAT) || !full_tiles_fit(B)) return 0;
     const int n_tiles = (int)(B / WAVE);
     if (w->capacity == 4) launch_chain<4, false>(w, q, n_tiles, pos, quat, nullptr, nullptr, s);
     else if (w->capacity == 8) launch_chain<8, false>(w, q, n_tiles, pos, quat, nullptr, nullptr, s);
@@ -451,7 +452,7 @@ int64_t launch_fk_fan_chains(const drm_walk *chains, int T, const float *q, int6
     return 0;
 #else
     const uint32_t al = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
-    if (T < 2 || T > 4 || al != (AL_Q | AL_POS | AL_QUAT) || B < WAVE || B / WAVE >= 0x7fffffffLL) return 0;
+    if (T < 2 || T > 4 || al != (AL_Q | AL_POS | AL_QUAT) || !full_tiles_fit(B)) return 0;
     FanChains tab;
     int longest = 0;
     const int cap = chains[0].capacity;

@@ -7,6 +7,7 @@
 // Per sample: in q[n] (4 n bytes), out H[n, n] (4 n^2 bytes).          n = 7: 28 + 196 = 224 B, ~2 kflop
 // 7-DoF arm chains run crba_arm_kernel below; every other robot the loop-structured kernel.
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 #include "drm_static.hpp"
@@ -345,9 +346,7 @@ static int64_t launch_crba_fingers_tree(const drm_walk *w, const float *q, int64
 #ifdef DRM_NO_CRBA_TREE
     return 0;
 #else
-    if (!(w->shape & DRM_WALK_FINGERS) || B / WAVE < DRM_CRBA_TREE_MIN_TILES || B / WAVE >= 0x7fffffffLL ||
-        (((uintptr_t)w->ops_f | (uintptr_t)H) & 15u) != 0)
-        return 0;
+    if (!(w->shape & DRM_WALK_FINGERS) || B / WAVE < DRM_CRBA_TREE_MIN_TILES || !full_tiles_fit(B) || !aligned16(w->ops_f, H)) return 0;
     const int K = DRM_WALK_AH_K(w->shape), L = DRM_WALK_AH_L(w->shape);
     if (K * L != w->n_ops || w->n_dofs != w->n_ops || K * L > 12) return 0;
     const int n_tiles = (int)(B / WAVE);
@@ -376,12 +375,21 @@ static int64_t launch_crba_fingers_tree(const drm_walk *w, const float *q, int64
 
 using namespace drm;
 
+// Does a straight-line kernel take this walk's full tiles when its pointers allow it?  Asked twice, and the two answers must
+// agree: the scratch query sizes such a walk's rows for fast_path_scratch_tiles(B) tiles of the loop kernel only, and the dispatch
+// holds the loop kernel's persistent grid on such a walk to MISALIGNED_TILES blocks — a grid larger than what the query sized
+// writes past the scratch.  The walk's OWN kernel (special[DRM_SPECIAL_CRBA]) counts here, unlike in drm_rnea and
+// drm_forward_dynamics: it needs H 16-byte aligned, so a misaligned call on such a walk does reach the loop kernel with all its
+// tiles, exactly like an arm's.
+static bool crba_straight_line(const drm_walk *w) {
+    return arm7_walk(w) || crba_arm_hand_applies(w) || w->special[DRM_SPECIAL_CRBA] != nullptr;
+}
+
 static int64_t drm_crba_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
     if (check_walk(w) || B <= 0 || !segments_ok(w)) return 0;
     // (full aligned tiles of these walks run straight-line kernels without scratch: sized for the ragged tail and for a misaligned
     // call, drm_common.hpp fast_path_scratch_tiles)
-    const bool fast = ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && w->n_dofs == 7) || crba_arm_hand_applies(w) ||
-                      w->special[DRM_SPECIAL_CRBA] != nullptr;
+    const bool fast = crba_straight_line(w);
     TreeArgs a;
     if (crba_short_plan(w, a)) return 0;
     CrbaRowsPlan p;
@@ -403,86 +411,66 @@ extern "C" int drm_crba(const drm_walk *w, const float *q, int64_t B, float *H, 
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs, nn = n * n;
     hipStream_t s = (hipStream_t)stream;
-    if (w->special[DRM_SPECIAL_CRBA] && B >= WAVE && B / WAVE < 0x7fffffffLL && (((uintptr_t)H | (uintptr_t)w->ops_f) & 15u) == 0) {
+    // what a rung leaves behind its full tiles: rows [done, B) re-enter with `rest`, the walk with that rung switched off
+    auto tail = [&](int64_t done, const drm_walk &rest) { return drm_crba(&rest, q + done * n, B - done, H + done * nn, scratch, stream); };
+    if (w->special[DRM_SPECIAL_CRBA] && full_tiles_fit(B) && aligned16(H, w->ops_f)) {
         // the robot's own straight-line kernel (csrc/drm_static.hpp crba_static_walk, built for exactly this walk): full tiles,
         // no scratch; q at any alignment, H 16-byte aligned (the tile's matrices leave as 16-byte stores)
         int n_tiles = (int)(B / WAVE);
-        void *args[] = {(void *)&w->ops_f, (void *)&q, (void *)&n_tiles, (void *)&H};
-        hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_CRBA], (unsigned)n_tiles, 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-        if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_crba_static): %s", hipGetErrorString(e));
+        rc = launch_module(w->special[DRM_SPECIAL_CRBA], (unsigned)n_tiles, WAVE, s, "drm_crba_static", w->ops_f, q, n_tiles, H);
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done == B) return DRM_OK;
-        drm_walk rest = *w;
-        rest.special[DRM_SPECIAL_CRBA] = nullptr;
-        return drm_crba(&rest, q + done * n, B - done, H + done * nn, scratch, stream);
+        return rc || done == B ? rc : tail(done, without_special(*w, DRM_SPECIAL_CRBA));
     }
 #ifndef DRM_NO_ARM_KERNEL
-    if ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7 && B >= WAVE && B / WAVE < 0x7fffffffLL &&
-        (((uintptr_t)q | (uintptr_t)H | (uintptr_t)w->ops_f) & 15u) == 0) {
+    if (arm7_walk(w) && full_tiles_fit(B) && aligned16(q, H, w->ops_f)) {
         // 7-DoF arms: full tiles through the packed-FP32 chain kernel, ragged tail through the generic one
         int n_tiles = (int)(B / WAVE);
         if (w->special[DRM_SPECIAL_CRBA_ARM]) {
             // this arm's own kernel, its constants folded into the instruction stream (csrc/drm_arm_static.hpp, specialize.py)
-            void *args[] = {(void *)&q, (void *)&n_tiles, (void *)&H};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_CRBA_ARM], (unsigned)n_tiles, 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_crba_arm_static): %s", hipGetErrorString(e));
+            rc = launch_module(w->special[DRM_SPECIAL_CRBA_ARM], (unsigned)n_tiles, WAVE, s, "drm_crba_arm_static", q, n_tiles, H);
+            if (rc) return rc;
         } else {
             const dim3 grid((unsigned)((n_tiles + MAX_WAVES_PER_BLOCK - 1) / MAX_WAVES_PER_BLOCK)), block(WAVE * MAX_WAVES_PER_BLOCK);
             if (arm_links(w) == 7) hipLaunchKernelGGL((crba_arm_kernel<8, 7, 7>), grid, block, 0, s, w->ops_f, q, n_tiles, H);
             else hipLaunchKernelGGL((crba_arm_kernel<8, 7, 8>), grid, block, 0, s, w->ops_f, q, n_tiles, H);
         }
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done == B) return launched();
         rc = launched();
-        if (rc) return rc;
-        drm_walk generic = *w;
-        generic.shape &= ~DRM_WALK_ARM_CHAIN;
-        return drm_crba(&generic, q + done * n, B - done, H + done * nn, scratch, stream);
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_ARM_CHAIN));
     }
 #endif
-    {   // an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through the straight-line kernel
-        const int64_t done = launch_crba_arm_hand(w, q, B, H, s);
-        if (done > 0) {
-            rc = launched();
-            if (rc || done == B) return rc;
-            drm_walk generic = *w;
-            generic.shape &= ~DRM_WALK_ARM_HAND;
-            return drm_crba(&generic, q + done * n, B - done, H + done * nn, scratch, stream);
-        }
+    // an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through the straight-line kernel
+    if (const int64_t done = launch_crba_arm_hand(w, q, B, H, s)) {
+        rc = launched();
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_ARM_HAND));
     }
-    {   // a small hand, a large launch: one wavefront per tile walks all the fingers
-        const int64_t done = launch_crba_fingers_tree(w, q, B, H, s);
-        if (done > 0) {
-            rc = launched();
-            if (rc || done == B) return rc;
-            return drm_crba(w, q + done * n, B - done, H + done * nn, scratch, stream); // (< 64 rows: the kernels below)
-        }
+    // a small hand, a large launch: one wavefront per tile walks all the fingers
+    if (const int64_t done = launch_crba_fingers_tree(w, q, B, H, s)) {
+        rc = launched();
+        return rc || done == B ? rc : tail(done, *w); // (< 64 rows: the kernels below)
     }
     // (a misaligned call on a walk with a straight-line kernel, or its ragged tail: the loop kernel on at most MISALIGNED_TILES blocks)
-    const bool fast_walk = ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7) || crba_arm_hand_applies(w) ||
-                           w->special[DRM_SPECIAL_CRBA] != nullptr;
+    const bool fast_walk = crba_straight_line(w);
     if (!segments_ok(w)) return fail(DRM_ERR_INVALID, "walk segments are inconsistent");
-    if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+    if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
     const int64_t tiles = (B + WAVE - 1) / WAVE;
-    if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     const uint32_t align = al16(q, AL_Q) | al16(H, AL_TAU);
     TreeArgs fingers;
     if (const size_t lds = crba_short_plan(w, fingers)) {
-        if (stream_past_llc(B * nn * (int64_t)sizeof(float))) { // beyond the Infinity Cache: sc1 nt stores
-            rc = ensure_lds_tree(crba_tree_kernel<true>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(crba_tree_kernel<true>, dim3((unsigned)tiles), dim3(WAVE * fingers.n_segments), lds, s, fingers, q, B, H, div_magic(n), align);
-        } else {
-            rc = ensure_lds_tree(crba_tree_kernel<false>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(crba_tree_kernel<false>, dim3((unsigned)tiles), dim3(WAVE * fingers.n_segments), lds, s, fingers, q, B, H, div_magic(n), align);
-        }
-        return launched();
+        auto go = [&](auto kernel) {
+            int e = ensure_lds_tree(kernel, lds);
+            if (e) return e;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(WAVE * fingers.n_segments), lds, s, fingers, q, B, H, div_magic(n), align);
+            return launched();
+        };
+        // beyond the Infinity Cache: sc1 nt stores
+        return stream_past_llc(B * nn * (int64_t)sizeof(float)) ? go(crba_tree_kernel<true>) : go(crba_tree_kernel<false>);
     }
     CrbaRowsPlan p;
     rc = crba_rows_plan(w, p);
     if (rc) return rc;
-    if (!scratch || ((uintptr_t)scratch & 15u))
+    if (!scratch || !aligned16(scratch))
         return fail(DRM_ERR_INVALID, "this robot's inertia matrix is assembled through scratch: pass drm_crba_scratch_floats() floats, 16-byte aligned");
     int64_t grid = tiles < p.resident ? tiles : (int64_t)p.resident;
     if (fast_walk && grid > MISALIGNED_TILES) grid = MISALIGNED_TILES;

@@ -5,6 +5,7 @@
 //
 // Per sample: in q[n] (4 n bytes), out pos[T,3] quat[T,4] (28 T bytes).
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 
@@ -294,10 +295,10 @@ extern "C" int drm_fk_links(const drm_walk *w, const float *q, int64_t B, int32_
     if (B < 0 || n_targets < 1) return fail(DRM_ERR_INVALID, "negative batch or no targets");
     if (n_targets > w->n_ops) return fail(DRM_ERR_INVALID, "more targets than ops in the walk");
     if (B == 0) return DRM_OK;
-    if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+    if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
     const int n = w->n_dofs, T = n_targets;
     const int64_t tiles = (B + WAVE - 1) / WAVE;
-    if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     // A wavefront per run of sub-trees behind the hub: every wavefront repeats the ops in front of the hub, and with ~8 KB of LDS
     // per tile the kernel is bound by instruction issue once the device is full (iiwa7 + Allegro at 2^20: 248 us fanned out,
     // eight of a wavefront's thirteen ops repeated) — so a walk with a shared part is fanned out only while the tiles do not
@@ -335,7 +336,7 @@ extern "C" int drm_fk_fanout(const drm_walk *chains, int32_t n_chains, const flo
         if (rc) return rc;
         if (w->capacity != chains[0].capacity || w->n_dofs != chains[0].n_dofs || w->n_slots != 0)
             return fail(DRM_ERR_INVALID, "fan-out chains must share capacity and n_dofs and have no branch points");
-        if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+        if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
         tab.ops_f[t] = w->ops_f;
         tab.ops_i[t] = w->ops_i;
         tab.n_ops[t] = w->n_ops;
@@ -353,7 +354,7 @@ extern "C" int drm_fk_fanout(const drm_walk *chains, int32_t n_chains, const flo
         }
     }
     const int64_t tiles = (B + WAVE - 1) / WAVE;
-    if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     const size_t lds = sizeof(float) * (size_t)(round4(WAVE * pad_odd(n)) + round4(WAVE * pad_odd(3 * T)) + round4(WAVE * pad_odd(4 * T)) +
                                                 T * table_lds_floats(max_ops));
     int rc = ensure_lds_tree(fk_fanout_kernel, lds);
@@ -387,7 +388,7 @@ extern "C" int drm_fk(const drm_walk *w, const float *q, int64_t B, int32_t n_ta
             return drm_fk(&generic, q + done * n, B - done, 1, pos + done * 3, quat + done * 4, stream);
         }
     }
-    if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+    if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
     TreeArgs a = tree_args(w);
     a.n_segments = 1; a.prefix_end = 0;
 #ifndef DRM_NO_FK_GROUPS
@@ -399,7 +400,7 @@ extern "C" int drm_fk(const drm_walk *w, const float *q, int64_t B, int32_t n_ta
             if (lds_fan <= (size_t)80 * 1024) {
                 const TreeArgs af = tree_args(w, false);
                 const int64_t tiles = (B + WAVE - 1) / WAVE;
-                if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+                if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
                 const uint32_t align = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
                 hipStream_t s = (hipStream_t)stream;
                 if (stream_past_llc(B * 28 * T)) {
@@ -420,7 +421,7 @@ extern "C" int drm_fk(const drm_walk *w, const float *q, int64_t B, int32_t n_ta
         const size_t lds = sizeof(float) * (size_t)(table_lds_floats(a.n_ops) + round4(WAVE * pad_odd(n)) + round4(WAVE * FK_GP) +
                                                     round4(WAVE * FK_GR) + w->n_slots * 12 * WAVE);
         const int64_t tiles = (B + WAVE - 1) / WAVE;
-        if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+        if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
         const uint32_t align = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
         hipStream_t s = (hipStream_t)stream;
         if (stream_past_llc(B * 28 * T)) {
@@ -440,7 +441,7 @@ extern "C" int drm_fk(const drm_walk *w, const float *q, int64_t B, int32_t n_ta
     rc = ensure_lds_tree(fk_tree_kernel, lds);
     if (rc) return rc;
     const int64_t tiles = (B + WAVE - 1) / WAVE;
-    if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     const uint32_t align = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(fk_tree_kernel, dim3((unsigned)tiles), dim3(WAVE), lds, s, a, q, B, T, pos, quat, div_magic(n), div_magic(3 * T),
@@ -469,12 +470,11 @@ extern "C" int drm_fk_fanout_links(const drm_walk *chains, int32_t n_chains, con
         const void *own = chains[0].special[DRM_SPECIAL_FK_FAN_LINKS];
         for (int t = 1; t < n_chains; ++t)
             if (chains[t].special[DRM_SPECIAL_FK_FAN_LINKS] != own) own = nullptr;
-        if (own && B >= WAVE && !(B & 3) && B / WAVE < 0x7fffffffLL && ((((uintptr_t)q | (uintptr_t)pos | (uintptr_t)quat) & 15u) == 0)) {
+        if (own && full_tiles_fit(B) && !(B & 3) && aligned16(q, pos, quat)) {
             const int64_t n_tiles = B / WAVE;
             int64_t rows = B;
-            void *args[] = {(void *)&q, (void *)&pos, (void *)&quat, (void *)&rows};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)own, (unsigned)n_tiles, 1, 1, WAVE * (unsigned)n_chains, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_fk_fan_links_static): %s", hipGetErrorString(e));
+            int rc = launch_module(own, (unsigned)n_tiles, WAVE * (unsigned)n_chains, (hipStream_t)stream, "drm_fk_fan_links_static", q, pos, quat, rows);
+            if (rc) return rc;
             done = n_tiles * WAVE;
         }
     }

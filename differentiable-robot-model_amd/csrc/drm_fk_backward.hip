@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 
 namespace drm {
@@ -677,9 +678,7 @@ static int fk_backward_launch(const drm_walk *w, const float *q, int64_t B, int3
     float *partials = scratch;
 #ifndef DRM_NO_ARM_KERNEL
     {
-        const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)grad_pos | (uintptr_t)grad_q | (uintptr_t)w->ops_f;
-        if (!jac && !grad_rot && T == 1 && (w->shape & DRM_WALK_ARM_CHAIN) && cap == 8 && n == 7 && (ptrs & 15u) == 0 && B >= WAVE &&
-            B / WAVE < 0x7fffffffLL) {
+        if (!jac && !grad_rot && T == 1 && arm7_walk(w) && aligned16(q, grad_pos, grad_q, w->ops_f) && full_tiles_fit(B)) {
             // 7-DoF arms, one target at the end of the chain: full tiles through the chain kernel, the ragged tail (if
             // any) through the generic kernel below with its rows of partial sums appended
             const int n_tiles = (int)(B / WAVE);
@@ -778,9 +777,7 @@ extern "C" int drm_fk_mse(const drm_walk *w, const float *q, const float *target
     if ((param_mask != 0) != (grad_ops_f != nullptr))
         return fail(DRM_ERR_INVALID, "grad_ops_f must be given exactly when param_mask selects ops");
     const int cap = w->capacity;
-    const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)target | (uintptr_t)grad_q | (uintptr_t)w->ops_f;
-    if (!((w->shape & DRM_WALK_ARM_CHAIN) && cap == 8 && w->n_dofs == 7 && (ptrs & 15u) == 0 && B >= WAVE && B % WAVE == 0 &&
-          B / WAVE < 0x7fffffffLL))
+    if (!(arm7_walk(w) && aligned16(q, target, grad_q, w->ops_f) && full_tiles_fit(B) && B % WAVE == 0))
         return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse takes 7-DoF arm chains (DRM_WALK_ARM_CHAIN, capacity 8), batches that are a "
                                          "multiple of 64 rows and 16-byte aligned pointers; compose drm_fk and drm_fk_backward otherwise%s", "");
     if (param_mask >> cap) return fail(DRM_ERR_INVALID, "param_mask selects ops beyond the walk's capacity");
@@ -818,9 +815,7 @@ extern "C" int drm_fk_mse_links(const drm_walk *w, const int32_t *sel, const flo
         return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse_links takes 1 .. %s%ld learnable links (%ld): compose drm_walk_table, drm_fk_mse, "
                                          "drm_walk_table_backward otherwise", "", (long)DRM_FK_MSE_MAX_LINKS, (long)n_links);
     const int cap = w->capacity;
-    const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)target | (uintptr_t)grad_q | (uintptr_t)w->ops_f | (uintptr_t)sel | (uintptr_t)gsign;
-    if (!((w->shape & DRM_WALK_ARM_CHAIN) && cap == 8 && w->n_dofs == 7 && (ptrs & 15u) == 0 && B >= WAVE && B % WAVE == 0 &&
-          B / WAVE < 0x7fffffffLL))
+    if (!(arm7_walk(w) && aligned16(q, target, grad_q, w->ops_f, sel, gsign) && full_tiles_fit(B) && B % WAVE == 0))
         return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse_links takes what drm_fk_mse takes: 7-DoF arm chains (capacity 8), batches that are a "
                                          "multiple of 64 rows, 16-byte aligned pointers%s", "");
     if (!param_mask || (param_mask >> cap)) return fail(DRM_ERR_INVALID, "param_mask must select ops of the walk (those of the learnable links)");

@@ -7,6 +7,7 @@
 //             out pos[3] quat[4] lin_jac[3,n] ang_jac[3,n] (4 (7 + 6 n) bytes)      n = 7: 224 B
 // LDS per wave: [ q tile : 64 (n|1) ][ staging : 64 max(3n|1, 3) ]
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 
@@ -114,8 +115,7 @@ extern "C" int drm_fk_jacobian(const drm_walk *w, const float *q, int64_t B, flo
 #ifdef DRM_NO_ARM_KERNEL
     if (false) {
 #else
-    if ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7 && w->target_perm == 2 && align == all_al &&
-        (((uintptr_t)w->ops_f) & 15u) == 0 && B >= WAVE && B / WAVE < 0x7fffffffLL) {
+    if (arm7_walk(w) && w->target_perm == 2 && align == all_al && table_aligned(w) && full_tiles_fit(B)) {
 #endif
         // 7-DoF arms (Franka Panda, KUKA iiwa): full tiles through the packed-FP32 chain kernel, ragged tail (if
         // any) through the generic one
@@ -142,7 +142,7 @@ extern "C" int drm_fk_jacobian(const drm_walk *w, const float *q, int64_t B, flo
             return drm_fk_jacobian(&generic, q + done * n, B - done, pos + done * 3, quat + done * 4, lin_jac + done * 3 * n,
                                    ang_jac + done * 3 * n, stream);
         }
-        if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+        if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
         TreeArgs a = tree_args(w);
         a.n_segments = 1; a.prefix_end = 0;
         const size_t lds = sizeof(float) * (size_t)(table_lds_floats(a.n_ops) + round4(WAVE * pad_odd(n)) + round4(WAVE * 3) +
@@ -150,7 +150,7 @@ extern "C" int drm_fk_jacobian(const drm_walk *w, const float *q, int64_t B, flo
         rc = ensure_lds_tree(fk_jacobian_tree_kernel, lds);
         if (rc) return rc;
         const int64_t tiles = (B + WAVE - 1) / WAVE;
-        if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+        if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
         hipLaunchKernelGGL(fk_jacobian_tree_kernel, dim3((unsigned)tiles), dim3(WAVE), lds, s, a, w->dof_mask, q, B, pos, quat, lin_jac,
                            ang_jac, div_magic(n), div_magic(3 * n), align, (int)w->target_perm);
     }

@@ -12,6 +12,7 @@
 //
 // Per sample: in q, qd, f [n] (12 n bytes), out qdd [n] (4 n bytes).          n = 7: 112 B
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 
@@ -369,11 +370,11 @@ static int64_t launch_forward_dynamics_fingers(const drm_walk *w, const float *q
 #ifdef DRM_NO_FINGERS_KERNEL
     return 0;
 #else
-    if (!(w->shape & DRM_WALK_FINGERS) || B < WAVE || B / WAVE >= 0x7fffffffLL || (((uintptr_t)w->ops_f) & 15u) != 0) return 0;
-    const int K = DRM_WALK_AH_K(w->shape), L = DRM_WALK_AH_L(w->shape), n = w->n_dofs;
-    if (K * L != w->n_ops || n != w->n_ops || K < 2 || K > 4 || L < 2 || L > 4) return 0;
-    const int n_tiles = (int)(B / WAVE);
-    const int vec = (n % 4 == 0) && ((((uintptr_t)q | (uintptr_t)qd | (uintptr_t)f | (uintptr_t)qdd) & 15u) == 0);
+    if (!(w->shape & DRM_WALK_FINGERS) || !full_tiles_fit(B) || !table_aligned(w)) return 0;
+    int K, L;
+    if (!fingers_shape(w, K, L)) return 0;
+    const int n = w->n_dofs, n_tiles = (int)(B / WAVE);
+    const int vec = (n % 4 == 0) && aligned16(q, qd, f, qdd);
 #define X(l)                                                                                                                     \
     if (L == l)                                                                                                                  \
         hipLaunchKernelGGL((forward_dynamics_fingers_kernel<l>), dim3((unsigned)n_tiles), dim3(WAVE * K), 0, s, w->ops_f, q, qd, f, n, \
@@ -388,13 +389,18 @@ static int64_t launch_forward_dynamics_fingers(const drm_walk *w, const float *q
 
 using namespace drm;
 
+// Do the library's straight-line kernels take this walk's full tiles when every pointer is 16-byte aligned?  Asked by the scratch
+// query and by the dispatch's cap on the articulated-body kernel's grid, which must agree — see rnea_straight_line (drm_rnea.hip), also
+// for why the walk's OWN kernel (special[DRM_SPECIAL_FD], any alignment: only ever leaves a tail of one tile) is not part of it.
+static bool forward_dynamics_straight_line(const drm_walk *w) { return arm7_walk(w) || arm_hand_compiled(w); }
+
 static int64_t drm_forward_dynamics_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
     if (check_walk(w) || B <= 0 || !segments_ok(w)) return 0;
     // (full aligned tiles of these walks run straight-line kernels without scratch: sized for the ragged tail and for a misaligned
     // call, drm_common.hpp fast_path_scratch_tiles)
-    if (w->special[DRM_SPECIAL_FD]) aligned = true;   // (the robot's own kernel takes any alignment: only a ragged tail is sized)
-    const bool fast = ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && w->n_dofs == 7) || arm_hand_compiled(w) ||
-                      w->special[DRM_SPECIAL_FD] != nullptr;
+    const bool own = w->special[DRM_SPECIAL_FD] != nullptr;
+    if (own) aligned = true;   // (the robot's own kernel takes any alignment: only a ragged tail is sized)
+    const bool fast = own || forward_dynamics_straight_line(w);
     TreeArgs a;
     if (fd_short_plan(w, a)) return 0;
     AbaPlan p;
@@ -416,99 +422,73 @@ extern "C" int drm_forward_dynamics(const drm_walk *w, const float *q, const flo
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs;
-    if (w->special[DRM_SPECIAL_FD] && B >= WAVE && B / WAVE < 0x7fffffffLL && (((uintptr_t)w->ops_f) & 15u) == 0) {
+    hipStream_t s = (hipStream_t)stream;
+    // what a rung leaves behind its full tiles: rows [done, B) re-enter with `rest`, the walk with that rung switched off
+    auto tail = [&](int64_t done, const drm_walk &rest) {
+        return drm_forward_dynamics(&rest, q + done * n, qd + done * n, f + done * n, B - done, flags, qdd + done * n, scratch, stream);
+    };
+    if (w->special[DRM_SPECIAL_FD] && full_tiles_fit(B) && table_aligned(w)) {
         // the robot's own straight-line articulated-body kernel (csrc/drm_static.hpp aba_static_walk, built for exactly this walk):
         // full tiles, any pointer alignment, no scratch
         int n_tiles = (int)(B / WAVE), fl = (int)flags;
         uint32_t magic = div_magic(n), al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(f, AL_QDD) | al16(qdd, AL_TAU);
-        void *args[] = {(void *)&w->ops_f, (void *)&q, (void *)&qd, (void *)&f, (void *)&n_tiles, (void *)&fl, (void *)&qdd, (void *)&magic, (void *)&al};
         int grid = 0; // persistent wavefronts: what the device holds at once
-        int rcg = resident_blocks_module((hipFunction_t)w->special[DRM_SPECIAL_FD], WAVE, grid);
-        if (rcg) return rcg;
+        rc = resident_blocks_module((hipFunction_t)w->special[DRM_SPECIAL_FD], WAVE, grid);
+        if (rc) return rc;
         if (grid > n_tiles || w->n_ops < STATIC_LONE_OPS) grid = n_tiles; // (small robots: one tile per block, drm_common.hpp STATIC_LONE_OPS)
-        hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_FD], (unsigned)grid, 1, 1, WAVE, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-        if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_fd_static): %s", hipGetErrorString(e));
+        rc = launch_module(w->special[DRM_SPECIAL_FD], (unsigned)grid, WAVE, s, "drm_fd_static", w->ops_f, q, qd, f, n_tiles, fl, qdd, magic, al);
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done == B) return DRM_OK;
-        drm_walk rest = *w;
-        rest.special[DRM_SPECIAL_FD] = nullptr;
-        return drm_forward_dynamics(&rest, q + done * n, qd + done * n, f + done * n, B - done, flags, qdd + done * n, scratch, stream);
+        return rc || done == B ? rc : tail(done, without_special(*w, DRM_SPECIAL_FD));
     }
-    {   // a hand (fingers off the root): full tiles through the per-finger arm form
-        const int64_t done = launch_forward_dynamics_fingers(w, q, qd, f, B, (int)flags, qdd, (hipStream_t)stream);
-        if (done > 0) {
-            rc = launched();
-            if (rc || done == B) return rc;
-            drm_walk generic = *w;
-            generic.shape &= ~DRM_WALK_FINGERS;
-            return drm_forward_dynamics(&generic, q + done * n, qd + done * n, f + done * n, B - done, flags, qdd + done * n, scratch, stream);
-        }
+    // a hand (fingers off the root): full tiles through the per-finger arm form
+    if (const int64_t done = launch_forward_dynamics_fingers(w, q, qd, f, B, (int)flags, qdd, s)) {
+        rc = launched();
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_FINGERS));
     }
 #ifndef DRM_NO_ARM_KERNEL
-    if ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7 && B >= WAVE && B / WAVE < 0x7fffffffLL &&
-        (((uintptr_t)q | (uintptr_t)qd | (uintptr_t)f | (uintptr_t)qdd | (uintptr_t)w->ops_f) & 15u) == 0) {
+    if (arm7_walk(w) && full_tiles_fit(B) && aligned16(q, qd, f, qdd, w->ops_f)) {
         // 7-DoF arms: full tiles through the register-resident chain kernel, ragged tail through the generic one
         int n_tiles = (int)(B / WAVE);
         if (w->special[DRM_SPECIAL_FD_ARM2] && w->special[DRM_SPECIAL_FD_ARM] && n_tiles / 2 >= DRM_ARM_STATIC_MIN_PAIRS) {
             // ABI 11: two samples per lane for the pairs of tiles of a large launch (issue-bound: a third fewer instructions per
             // sample); an odd last tile and the ragged tail follow through the forms below
             int n_pairs = n_tiles / 2, fl = (int)flags;
-            void *args[] = {(void *)&q, (void *)&qd, (void *)&f, (void *)&n_pairs, (void *)&fl, (void *)&qdd};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_FD_ARM2], (unsigned)n_pairs, 1, 1, WAVE, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_fd_arm2_static): %s", hipGetErrorString(e));
-            const int64_t done2 = (int64_t)n_pairs * 2 * WAVE;
-            if (done2 == B) return launched();
-            rc = launched();
+            rc = launch_module(w->special[DRM_SPECIAL_FD_ARM2], (unsigned)n_pairs, WAVE, s, "drm_fd_arm2_static", q, qd, f, n_pairs, fl, qdd);
             if (rc) return rc;
-            drm_walk rest = *w;
-            rest.special[DRM_SPECIAL_FD_ARM2] = nullptr;
-            return drm_forward_dynamics(&rest, q + done2 * n, qd + done2 * n, f + done2 * n, B - done2, flags, qdd + done2 * n, scratch, stream);
+            const int64_t done2 = (int64_t)n_pairs * 2 * WAVE;
+            rc = launched();
+            return rc || done2 == B ? rc : tail(done2, without_special(*w, DRM_SPECIAL_FD_ARM2));
         }
         const dim3 grid((unsigned)((n_tiles + MAX_WAVES_PER_BLOCK - 1) / MAX_WAVES_PER_BLOCK)), block(WAVE * MAX_WAVES_PER_BLOCK);
         if (w->special[DRM_SPECIAL_FD_ARM]) {
             // this arm's own kernel, its constants folded into the instruction stream (csrc/drm_arm_static.hpp, specialize.py)
             int fl = (int)flags;
-            void *args[] = {(void *)&q, (void *)&qd, (void *)&f, (void *)&n_tiles, (void *)&fl, (void *)&qdd};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_FD_ARM], (unsigned)n_tiles, 1, 1, WAVE, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_fd_arm_static): %s", hipGetErrorString(e));
+            rc = launch_module(w->special[DRM_SPECIAL_FD_ARM], (unsigned)n_tiles, WAVE, s, "drm_fd_arm_static", q, qd, f, n_tiles, fl, qdd);
+            if (rc) return rc;
         } else if (arm_links(w) == 7)
-            hipLaunchKernelGGL((forward_dynamics_arm_kernel<8, 7, 7>), grid, block, 0, (hipStream_t)stream, w->ops_f, q, qd, f,
-                               n_tiles, (int)flags, qdd);
+            hipLaunchKernelGGL((forward_dynamics_arm_kernel<8, 7, 7>), grid, block, 0, s, w->ops_f, q, qd, f, n_tiles, (int)flags, qdd);
         else
-            hipLaunchKernelGGL((forward_dynamics_arm_kernel<8, 7, 8>), grid, block, 0, (hipStream_t)stream, w->ops_f, q, qd, f,
-                               n_tiles, (int)flags, qdd);
+            hipLaunchKernelGGL((forward_dynamics_arm_kernel<8, 7, 8>), grid, block, 0, s, w->ops_f, q, qd, f, n_tiles, (int)flags, qdd);
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done == B) return launched();
         rc = launched();
-        if (rc) return rc;
-        drm_walk generic = *w;
-        generic.shape &= ~DRM_WALK_ARM_CHAIN;
-        return drm_forward_dynamics(&generic, q + done * n, qd + done * n, f + done * n, B - done, flags, qdd + done * n,
-                                    scratch, stream);
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_ARM_CHAIN));
     }
 #endif
-    {   // an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through the straight-line kernel
-        const int64_t done = launch_forward_dynamics_arm_hand(w, q, qd, f, B, (int)flags, qdd, (hipStream_t)stream);
-        if (done > 0) {
-            rc = launched();
-            if (rc || done == B) return rc;
-            drm_walk generic = *w;
-            generic.shape &= ~DRM_WALK_ARM_HAND;
-            return drm_forward_dynamics(&generic, q + done * n, qd + done * n, f + done * n, B - done, flags, qdd + done * n, scratch,
-                                        stream);
-        }
+    // an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through the straight-line kernel
+    if (const int64_t done = launch_forward_dynamics_arm_hand(w, q, qd, f, B, (int)flags, qdd, s)) {
+        rc = launched();
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_ARM_HAND));
     }
     // (as in drm_rnea: a misaligned call on a walk with a straight-line kernel, or its ragged tail, runs the loop kernel on at most
     // MISALIGNED_TILES blocks — what its scratch is sized for)
-    const bool fast_walk = (((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7)) || arm_hand_compiled(w);
+    const bool fast_walk = forward_dynamics_straight_line(w);
     if (!segments_ok(w)) return fail(DRM_ERR_INVALID, "walk segments are inconsistent");
-    if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+    if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
     const int64_t tiles = (B + WAVE - 1) / WAVE;
-    if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
-    hipStream_t s = (hipStream_t)stream;
+    if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(f, AL_QDD) | al16(qdd, AL_TAU);
     TreeArgs fingers;
     if (const size_t lds = fd_short_plan(w, fingers)) {
-        const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(f, AL_QDD) | al16(qdd, AL_TAU);
         rc = ensure_lds_tree(forward_dynamics_tree_kernel, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(forward_dynamics_tree_kernel, dim3((unsigned)tiles), dim3(WAVE * fingers.n_segments), lds, s, fingers, (int)flags,
@@ -520,7 +500,6 @@ extern "C" int drm_forward_dynamics(const drm_walk *w, const float *q, const flo
     if (rc) return rc;
     if (!scratch)
         return fail(DRM_ERR_INVALID, "this robot runs the articulated-body kernel: pass drm_forward_dynamics_scratch_floats() floats of scratch");
-    const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(f, AL_QDD) | al16(qdd, AL_TAU);
     int64_t grid = tiles < p.resident ? tiles : (int64_t)p.resident;
     if (fast_walk && grid > MISALIGNED_TILES) grid = MISALIGNED_TILES;
     hipLaunchKernelGGL(forward_dynamics_aba_kernel, dim3((unsigned)grid), dim3(WAVE * p.a.n_segments), p.lds, s, p.a, (int)flags, q, qd, f, B,

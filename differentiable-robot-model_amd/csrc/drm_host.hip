@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_link_forms.hpp"
 
@@ -44,7 +45,7 @@ int make_geometry(int64_t B, int lds_floats_per_wave, Geometry &g) {
     while (wpb > 1 && per_wave * wpb > (size_t)64 * 1024) wpb >>= 1;
     const int64_t tiles = (B + WAVE - 1) / WAVE;
     const int64_t blocks = (tiles + wpb - 1) / wpb;
-    if (blocks > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (!grid_fits(blocks)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     g.grid = dim3((unsigned)blocks);
     g.block = dim3(WAVE * wpb);
     g.lds_per_wave = round4(lds_floats_per_wave);

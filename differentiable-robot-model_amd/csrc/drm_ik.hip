@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_ik.hpp"
 #include "drm_sample.hpp"
 
@@ -186,8 +187,7 @@ __global__ void __launch_bounds__(64)
 
 // the fused kernel takes the full tiles of this walk (the rows where drm_fk_jacobian itself launches the arm kernel)
 static bool ik_fused(const drm_walk *w, int64_t B, bool aligned) {
-    return (w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && w->n_dofs == 7 && w->target_perm == 2 && aligned &&
-           (((uintptr_t)w->ops_f) & 15u) == 0 && B >= WAVE && B / WAVE < 0x7fffffffLL;
+    return arm7_walk(w) && w->target_perm == 2 && aligned && table_aligned(w) && full_tiles_fit(B);
 }
 
 // scratch of the composed path over `rows` rows: pos, quat, lin, ang of drm_fk_jacobian, its input qfk and the done flags, each
@@ -245,8 +245,7 @@ extern "C" int drm_inverse_kinematics(const drm_walk *w, const float *q0, const 
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;
     const IkOpts o = {damping * damping, step, tol_pos, tol_rot};
-    const bool aligned = ((((uintptr_t)q0 | (uintptr_t)target_pos | (uintptr_t)target_quat | (uintptr_t)q | (uintptr_t)err |
-                            (uintptr_t)iters) & 15u) == 0);
+    const bool aligned = aligned16(q0, target_pos, target_quat, q, err, iters);
     int64_t lo = 0;
     if (!(flags & DRM_IK_COMPOSED) && ik_fused(w, B, aligned)) {
         const int n_tiles = (int)(B / WAVE);
@@ -260,7 +259,7 @@ extern "C" int drm_inverse_kinematics(const drm_walk *w, const float *q0, const 
     // the composed path over rows [lo, B)
     if (!scratch) return fail(DRM_ERR_INVALID, "pass drm_inverse_kinematics_scratch_floats() floats of scratch");
     const int64_t rows = B - lo;
-    if (rows / 64 >= 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (rows / 64 >= GRID_MAX) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     const IkScratch L = ik_scratch_layout(rows, n);
     float *pos = scratch + L.pos, *quat = scratch + L.quat, *lin = scratch + L.lin, *ang = scratch + L.ang;
     float *qfk = scratch + L.qfk;

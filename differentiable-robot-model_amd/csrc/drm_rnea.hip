@@ -7,6 +7,7 @@
 // Per sample: in q, qd, qdd [n] (12 n bytes), out tau[n] (4 n bytes).   n = 7: 112 B, ~2.6 kflop.
 // 7-DoF arm chains run rnea_arm_kernel (drm_arm_kernels.hip); every other robot the loop-structured kernel below.
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 
@@ -176,14 +177,24 @@ static int rnea_records_plan(const drm_walk *w, RneaRecordsPlan &p) {
 
 using namespace drm;
 
+// Do the library's straight-line kernels (7-DoF arm, arm with a hand) take this walk's full tiles when every pointer is 16-byte
+// aligned?  Asked twice, and the two answers must agree: the scratch query sizes the records of such a walk for
+// fast_path_scratch_tiles(B) tiles of the loop kernel only, and the dispatch holds the loop kernel's persistent grid on such a walk
+// to MISALIGNED_TILES blocks — a grid larger than what the query sized writes records past the scratch.
+// The walk's OWN kernel (special[DRM_SPECIAL_RNEA]) is deliberately not part of it.  It takes full tiles at any pointer
+// alignment, so the query sizes exactly the one tile of a ragged tail for it; the dispatch reaches the loop kernel with such a
+// walk only with fewer than 64 rows (the own kernel's rung took the rest, or B was that small), i.e. with a grid of one block,
+// which the MISALIGNED_TILES cap cannot touch.
+static bool rnea_straight_line(const drm_walk *w) { return arm7_walk(w) || arm_hand_compiled(w); }
+
 static int64_t drm_rnea_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
     if (check_walk(w) || B <= 0 || !segments_ok(w)) return 0;
     // (7-DoF arms / arms with a hand: full aligned tiles run straight-line kernels without scratch; sized for the ragged tail and
     // for a misaligned call, drm_common.hpp fast_path_scratch_tiles)
     // (a walk with its own straight-line kernel, drm_walk.special: no alignment condition at all — only the ragged tail is sized)
-    if (w->special[DRM_SPECIAL_RNEA]) aligned = true;
-    const bool fast = ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && w->n_dofs == 7) || arm_hand_compiled(w) ||
-                      w->special[DRM_SPECIAL_RNEA] != nullptr;
+    const bool own = w->special[DRM_SPECIAL_RNEA] != nullptr;
+    if (own) aligned = true;
+    const bool fast = own || rnea_straight_line(w);
     TreeArgs a;
     if (rnea_short_plan(w, a)) return 0;
     RneaRecordsPlan p;
@@ -207,83 +218,59 @@ extern "C" int drm_rnea(const drm_walk *w, const float *q, const float *qd, cons
     const int n = w->n_dofs;
     const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(tau, AL_TAU);
     hipStream_t s = (hipStream_t)stream;
-    if (w->special[DRM_SPECIAL_RNEA] && B >= WAVE && B / WAVE < 0x7fffffffLL && (((uintptr_t)w->ops_f) & 15u) == 0) {
+    // what a rung leaves behind its full tiles: rows [done, B) re-enter with `rest`, the walk with that rung switched off
+    auto tail = [&](int64_t done, const drm_walk &rest) {
+        return drm_rnea(&rest, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n, scratch, stream);
+    };
+    if (w->special[DRM_SPECIAL_RNEA] && full_tiles_fit(B) && table_aligned(w)) {
         // a per-robot straight-line kernel built for exactly this walk (csrc/drm_static.hpp, specialize.py): full tiles, any
         // pointer alignment, no scratch; the ragged tail through the kernels below
         int n_tiles = (int)(B / WAVE), fl = (int)flags;
         uint32_t magic = div_magic(n), al = align;
-        void *args[] = {(void *)&w->ops_f, (void *)&q, (void *)&qd, (void *)&qdd, (void *)&n_tiles, (void *)&fl, (void *)&tau, (void *)&magic, (void *)&al};
         int grid = 0; // persistent wavefronts: what the device holds at once (each reads its next tile's rows while it walks one)
         rc = resident_blocks_module((hipFunction_t)w->special[DRM_SPECIAL_RNEA], WAVE, grid);
         if (rc) return rc;
         if (grid > n_tiles || w->n_ops < STATIC_LONE_OPS) grid = n_tiles; // (small robots: one tile per block, drm_common.hpp STATIC_LONE_OPS)
-        hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_RNEA], (unsigned)grid, 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-        if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_rnea_static): %s", hipGetErrorString(e));
+        rc = launch_module(w->special[DRM_SPECIAL_RNEA], (unsigned)grid, WAVE, s, "drm_rnea_static", w->ops_f, q, qd, qdd, n_tiles, fl, tau, magic, al);
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done == B) return DRM_OK;
-        drm_walk rest = *w;
-        rest.special[DRM_SPECIAL_RNEA] = nullptr;
-        return drm_rnea(&rest, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n, scratch, stream);
+        return rc || done == B ? rc : tail(done, without_special(*w, DRM_SPECIAL_RNEA));
     }
 #ifndef DRM_NO_ARM_KERNEL
-    if ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7 && B >= WAVE && B / WAVE < 0x7fffffffLL &&
-        align == (AL_Q | AL_QD | AL_TAU | (qdd ? AL_QDD : 0u)) && (((uintptr_t)w->ops_f) & 15u) == 0) {
+    if (arm7_walk(w) && full_tiles_fit(B) && align == (AL_Q | AL_QD | AL_TAU | (qdd ? AL_QDD : 0u)) && table_aligned(w)) {
         // 7-DoF arms: full tiles through the packed-FP32 chain kernel, ragged tail through the generic one
         if (w->special[DRM_SPECIAL_RNEA_ARM] && B / (2 * WAVE) >= DRM_ARM_STATIC_MIN_PAIRS) {
             // this arm's own kernel, its constants folded into the instruction stream (csrc/drm_arm_stream.hpp, specialize.py): the
             // 128-row pairs of tiles; an odd tile and the ragged tail through the kernels below
             int n_pairs = (int)(B / (2 * WAVE)), fl = (int)flags;
-            void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&n_pairs, (void *)&fl, (void *)&tau};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_RNEA_ARM], (unsigned)arm_stream_grid(n_pairs), 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_rnea_arm_static): %s", hipGetErrorString(e));
+            rc = launch_module(w->special[DRM_SPECIAL_RNEA_ARM], (unsigned)arm_stream_grid(n_pairs), WAVE, s, "drm_rnea_arm_static", q, qd, qdd, n_pairs, fl, tau);
             const int64_t done = (int64_t)n_pairs * 2 * WAVE;
-            if (done == B) return DRM_OK;
-            drm_walk rest = *w;
-            rest.special[DRM_SPECIAL_RNEA_ARM] = nullptr;
-            return drm_rnea(&rest, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n, scratch, stream);
+            return rc || done == B ? rc : tail(done, without_special(*w, DRM_SPECIAL_RNEA_ARM));
         }
         const int n_tiles = (int)(B / WAVE);
         launch_rnea_arm(w->ops_f, arm_links(w), q, qd, qdd, n_tiles, (int)flags, tau, s);
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done == B) return launched();
         rc = launched();
-        if (rc) return rc;
-        drm_walk generic = *w;
-        generic.shape &= ~DRM_WALK_ARM_CHAIN;
-        return drm_rnea(&generic, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags,
-                        tau + done * n, scratch, stream);
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_ARM_CHAIN));
     }
 #endif
-    {   // a hand (fingers off the root): full 128-row tiles through the two-samples-per-lane finger kernel
-        const int64_t done = launch_rnea_fingers(w, q, qd, qdd, B, (int)flags, tau, s);
-        if (done > 0) {
-            rc = launched();
-            if (rc || done == B) return rc;
-            drm_walk generic = *w;
-            generic.shape &= ~DRM_WALK_FINGERS;
-            return drm_rnea(&generic, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n,
-                            scratch, stream);
-        }
+    // a hand (fingers off the root): full 128-row tiles through the two-samples-per-lane finger kernel
+    if (const int64_t done = launch_rnea_fingers(w, q, qd, qdd, B, (int)flags, tau, s)) {
+        rc = launched();
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_FINGERS));
     }
-    {   // an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through the straight-line kernel
-        const int64_t done = launch_rnea_arm_hand(w, q, qd, qdd, B, (int)flags, tau, s);
-        if (done > 0) {
-            rc = launched();
-            if (rc || done == B) return rc;
-            drm_walk generic = *w;
-            generic.shape &= ~DRM_WALK_ARM_HAND;
-            return drm_rnea(&generic, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n,
-                            scratch, stream);
-        }
+    // an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through the straight-line kernel
+    if (const int64_t done = launch_rnea_arm_hand(w, q, qd, qdd, B, (int)flags, tau, s)) {
+        rc = launched();
+        return rc || done == B ? rc : tail(done, without_shape(*w, DRM_WALK_ARM_HAND));
     }
     // A walk whose full tiles would have run a straight-line kernel got here because its pointers are not 16-byte aligned (or as
     // the ragged tail of such a call): its scratch holds fast_path_scratch_tiles(B) tiles of the loop kernel — the persistent grid
     // below is held to that many blocks.
-    const bool fast_walk = (((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7)) || arm_hand_compiled(w);
+    const bool fast_walk = rnea_straight_line(w);
     if (!segments_ok(w)) return fail(DRM_ERR_INVALID, "walk segments are inconsistent");
-    if ((((uintptr_t)w->ops_f) & 15u) != 0) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
+    if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
     const int64_t tiles = (B + WAVE - 1) / WAVE;
-    if (tiles > 0x7fffffffLL) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
+    if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
     TreeArgs fingers;
     if (const size_t lds = rnea_short_plan(w, fingers)) {
         rc = ensure_lds_tree(rnea_tree_kernel, lds);
@@ -304,9 +291,9 @@ extern "C" int drm_rnea(const drm_walk *w, const float *q, const float *qd, cons
     return launched();
 }
 
-extern "C" int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t target_op, const float *q, const float *qd,
-                           const float *qdd, int64_t B, int32_t flags, float *tau, float *pos, float *quat, float *scratch,
-                           void *stream) {
+// The argument checks drm_fk_rnea and drm_fk_rnea_put share (B == 0 is the caller's to answer).
+static int fk_rnea_check(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, const float *tau, const float *pos,
+                         const float *quat, int64_t B) {
     int rc = check_walk(tree);
     if (rc) return rc;
     rc = check_walk(chain);
@@ -314,44 +301,53 @@ extern "C" int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t 
     if (!q || !qd || !tau || !pos || !quat) return fail(DRM_ERR_INVALID, "q / qd / tau / pos / quat must not be NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (tree->n_dofs != chain->n_dofs) return fail(DRM_ERR_INVALID, "the two walks belong to different robots");
-    if (B == 0) return DRM_OK;
+    return DRM_OK;
+}
+
+// The fused arm kernels (FK of the last link + inverse dynamics in one pass) apply to the full tiles of this call:
+// a serial 7-DoF arm whose last link is the target.  Two shapes: the tree walk IS the chain (target_op its last op: `same`), or
+// the tree walk holds the moving joints only (the host folded the fixed tail into the last of them).  Either way the
+// dynamics rows come from the TREE walk's table and only the fixed tail the FK chain still walks from the CHAIN walk's.
+static bool fk_rnea_arm_applies(const drm_walk *tree, const drm_walk *chain, int32_t target_op, int64_t B, const float *q, const float *qd,
+                                const float *qdd, const float *tau, const float *pos, const float *quat, bool &same) {
+    const int n = tree->n_dofs;
+    same = target_op == tree->n_ops - 1 && tree->n_ops == chain->n_ops;
+    const bool folded = tree->n_ops == n && chain->n_ops > n && (chain->shape & DRM_WALK_ARM_CHAIN) && chain->capacity == 8;
+    return arm7_walk(tree) && (same || folded) && chain->target_perm == 2 && full_tiles_fit(B) && aligned16(q, qd, qdd, tau, pos, quat);
+}
+
+extern "C" int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t target_op, const float *q, const float *qd,
+                           const float *qdd, int64_t B, int32_t flags, float *tau, float *pos, float *quat, float *scratch,
+                           void *stream) {
+    int rc = fk_rnea_check(tree, chain, q, qd, tau, pos, quat, B);
+    if (rc || B == 0) return rc;
+#ifndef DRM_NO_ARM_KERNEL
     const int n = tree->n_dofs;
     hipStream_t s = (hipStream_t)stream;
-#ifndef DRM_NO_ARM_KERNEL
-    const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(tau, AL_TAU) | al16(pos, AL_POS) |
-                           al16(quat, AL_QUAT);
-    // a serial 7-DoF arm whose last link is the target.  Two shapes: the tree walk IS the chain (target_op its last op), or
-    // the tree walk holds the moving joints only (the host folded the fixed tail into the last of them).  Either way the
-    // dynamics rows come from the TREE walk's table and only the fixed tail the FK chain still walks from the CHAIN walk's.
-    const bool same = target_op == tree->n_ops - 1 && tree->n_ops == chain->n_ops;
-    const bool folded = tree->n_ops == n && chain->n_ops > n && (chain->shape & DRM_WALK_ARM_CHAIN) && chain->capacity == 8;
-    if ((tree->shape & DRM_WALK_ARM_CHAIN) && tree->capacity == 8 && n == 7 && (same || folded) &&
-        chain->target_perm == 2 && B >= WAVE && B / WAVE < 0x7fffffffLL && (((uintptr_t)tree->ops_f) & 15u) == 0 &&
-        (((uintptr_t)chain->ops_f) & 15u) == 0 &&
-        align == (AL_Q | AL_QD | AL_TAU | AL_POS | AL_QUAT | (qdd ? AL_QDD : 0u))) {
+    // rows [done, B) re-enter with the two walks as given (fewer than 64 rows: the two walks one after the other, below)
+    auto tail = [&](int64_t done, const drm_walk &t2, const drm_walk &c2) {
+        return drm_fk_rnea(&t2, &c2, target_op, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n,
+                           pos + done * 3, quat + done * 4, scratch, stream);
+    };
+    bool same;
+    if (fk_rnea_arm_applies(tree, chain, target_op, B, q, qd, qdd, tau, pos, quat, same) && table_aligned(tree) && table_aligned(chain)) {
         if (tree->special[DRM_SPECIAL_FK_RNEA_ARM] && tree->special[DRM_SPECIAL_FK_RNEA_ARM] == chain->special[DRM_SPECIAL_FK_RNEA_ARM] &&
             B / (2 * WAVE) >= DRM_ARM_STATIC_MIN_PAIRS) {
             // the constant-folded fused kernel built for exactly this (dynamics walk, target chain) pair: the same handle on both
             int n_pairs = (int)(B / (2 * WAVE)), fl = (int)flags;
-            void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&n_pairs, (void *)&fl, (void *)&tau, (void *)&pos, (void *)&quat};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)tree->special[DRM_SPECIAL_FK_RNEA_ARM], (unsigned)arm_stream_grid(n_pairs), 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_fk_rnea_arm_static): %s", hipGetErrorString(e));
+            rc = launch_module(tree->special[DRM_SPECIAL_FK_RNEA_ARM], (unsigned)arm_stream_grid(n_pairs), WAVE, s, "drm_fk_rnea_arm_static", q, qd,
+                               qdd, n_pairs, fl, tau, pos, quat);
             const int64_t done = (int64_t)n_pairs * 2 * WAVE;
-            if (done == B) return DRM_OK;
-            drm_walk t2 = *tree, c2 = *chain;
-            t2.special[DRM_SPECIAL_FK_RNEA_ARM] = nullptr;
+            if (rc || done == B) return rc;
+            drm_walk t2 = without_special(*tree, DRM_SPECIAL_FK_RNEA_ARM);
             t2.special[DRM_SPECIAL_RNEA_ARM] = nullptr; // (a tail of less than a pair of tiles never reaches it anyway)
-            c2.special[DRM_SPECIAL_FK_RNEA_ARM] = nullptr;
-            return drm_fk_rnea(&t2, &c2, target_op, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, tau + done * n,
-                               pos + done * 3, quat + done * 4, scratch, stream);
+            return tail(done, t2, without_special(*chain, DRM_SPECIAL_FK_RNEA_ARM));
         }
         const int n_tiles = (int)(B / WAVE);
         launch_fk_rnea_arm(tree->ops_f, chain->ops_f, same ? arm_links(tree) : n, q, qd, qdd, n_tiles, (int)flags, tau, pos, quat, s);
         rc = launched();
         const int64_t done = (int64_t)n_tiles * WAVE;
-        if (rc || done == B) return rc;
-        q += done * n; qd += done * n; qdd = qdd ? qdd + done * n : nullptr;
-        tau += done * n; pos += done * 3; quat += done * 4; B -= done;
+        return rc || done == B ? rc : tail(done, *tree, *chain);
     }
 #endif
     // every other robot (and a ragged tail): the two walks one after the other on the same stream
@@ -369,14 +365,8 @@ extern "C" int drm_fk_rnea_put(const drm_walk *tree, const drm_walk *chain, int3
     if (!put || put->n_peers == 0) return drm_fk_rnea(tree, chain, target_op, q, qd, qdd, B, flags, tau, pos, quat, scratch, stream);
     if (put->n_peers < 0 || put->n_peers > DRM_MAX_PEERS || put->row_offset < 0)
         return fail(DRM_ERR_INVALID, "drm_put: n_peers must be 0 .. DRM_MAX_PEERS and row_offset >= 0");
-    int rc = check_walk(tree);
-    if (rc) return rc;
-    rc = check_walk(chain);
-    if (rc) return rc;
-    if (!q || !qd || !tau || !pos || !quat) return fail(DRM_ERR_INVALID, "q / qd / tau / pos / quat must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (tree->n_dofs != chain->n_dofs) return fail(DRM_ERR_INVALID, "the two walks belong to different robots");
-    if (B == 0) return DRM_OK;
+    int rc = fk_rnea_check(tree, chain, q, qd, tau, pos, quat, B);
+    if (rc || B == 0) return rc;
     const int n = tree->n_dofs;
     hipStream_t s = (hipStream_t)stream;
     int64_t done = 0;
@@ -384,29 +374,22 @@ extern "C" int drm_fk_rnea_put(const drm_walk *tree, const drm_walk *chain, int3
     {
         uintptr_t dst = 0;
         for (int p = 0; p < put->n_peers; ++p) dst |= (uintptr_t)put->tau[p] | (uintptr_t)put->pos[p] | (uintptr_t)put->quat[p];
-        const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(tau, AL_TAU) | al16(pos, AL_POS) | al16(quat, AL_QUAT);
-        const bool same = target_op == tree->n_ops - 1 && tree->n_ops == chain->n_ops;
-        const bool folded = tree->n_ops == n && chain->n_ops > n && (chain->shape & DRM_WALK_ARM_CHAIN) && chain->capacity == 8;
+        bool same;
         const void *own = tree->special[DRM_SPECIAL_FK_RNEA_ARM_PUT];
-        if (own && own == chain->special[DRM_SPECIAL_FK_RNEA_ARM_PUT] && (tree->shape & DRM_WALK_ARM_CHAIN) && tree->capacity == 8 && n == 7 &&
-            (same || folded) && chain->target_perm == 2 && B / (2 * WAVE) >= DRM_ARM_STATIC_MIN_PAIRS && B / WAVE < 0x7fffffffLL &&
-            align == (AL_Q | AL_QD | AL_TAU | AL_POS | AL_QUAT | (qdd ? AL_QDD : 0u)) && (dst & 15u) == 0 && (put->row_offset & 3) == 0) {
+        if (own && own == chain->special[DRM_SPECIAL_FK_RNEA_ARM_PUT] && fk_rnea_arm_applies(tree, chain, target_op, B, q, qd, qdd, tau, pos, quat, same) &&
+            B / (2 * WAVE) >= DRM_ARM_STATIC_MIN_PAIRS && (dst & 15u) == 0 && (put->row_offset & 3) == 0) {
             int n_pairs = (int)(B / (2 * WAVE)), fl = (int)flags;
             drm_put dsts = *put;
-            void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&n_pairs, (void *)&fl, (void *)&tau, (void *)&pos, (void *)&quat, (void *)&dsts};
-            hipError_t e = hipModuleLaunchKernel((hipFunction_t)own, (unsigned)arm_stream_grid(n_pairs), 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-            if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_fk_rnea_arm_put_static): %s", hipGetErrorString(e));
+            rc = launch_module(own, (unsigned)arm_stream_grid(n_pairs), WAVE, s, "drm_fk_rnea_arm_put_static", q, qd, qdd, n_pairs, fl, tau, pos, quat, dsts);
             done = (int64_t)n_pairs * 2 * WAVE;
-            if (done == B) return DRM_OK;
+            if (rc || done == B) return rc;
         }
     }
 #endif
     // what is left (everything, for walks without the in-kernel form): compute, then one copy per destination and array
-    const float *rq = q + done * n, *rqd = qd + done * n, *rqdd = qdd ? qdd + done * n : nullptr;
     float *rtau = tau + done * n, *rpos = pos + done * 3, *rquat = quat + done * 4;
     const int64_t rest = B - done, at = put->row_offset + done;
-    drm_walk t2 = *tree, c2 = *chain;
-    rc = drm_fk_rnea(&t2, &c2, target_op, rq, rqd, rqdd, rest, flags, rtau, rpos, rquat, scratch, stream);
+    rc = drm_fk_rnea(tree, chain, target_op, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, rest, flags, rtau, rpos, rquat, scratch, stream);
     if (rc) return rc;
     for (int p = 0; p < put->n_peers; ++p) {
         hipError_t e = hipSuccess;

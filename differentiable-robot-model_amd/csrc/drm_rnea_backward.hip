@@ -16,6 +16,7 @@
 // LDS per wave: [ q -> grad_q, qd -> grad_qd, qdd -> grad_qdd, grad_tau : 4 x 64 (n|1) ][ constant-gradient sums : cap*32 ]
 //               [ slots : n_slots*36*64 ][ records : (n_ops*2 + n_leaves*18)*64 unless PARK_HBM ]
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 
@@ -473,6 +474,212 @@ extern "C" int64_t drm_rnea_backward_scratch_floats(int64_t B, int32_t capacity,
     return floats;
 }
 
+// One call's operands, for the helpers below (every launch of the entry point passes the same ones on)
+struct RneaBackwardCall {
+    const drm_walk *w;
+    const float *q, *qd, *qdd, *grad_tau;
+    int64_t B;
+    int flags;
+    uint64_t param_mask;
+    float *grad_q, *grad_qd, *grad_qdd, *grad_ops_f, *partials;
+    hipStream_t s;
+};
+
+static size_t rnea_backward_lds_floats(const drm_walk *w, bool park_hbm) {
+    return rnea_backward_lds_floats(w->n_dofs, w->n_slots, w->capacity, w->n_ops, DRM_WALK_LEAVES(w->shape), park_hbm);
+}
+
+// rows [done, B) through the loop kernel in geometry g: its rows of partial sums from `prow` on, its records in LDS or (hbm) at `park`
+static int launch_rnea_backward_loop(const RneaBackwardCall &c, const Geometry &g, int64_t done, float *prow, float *park, uint32_t align,
+                                     bool hbm) {
+    const drm_walk *w = c.w;
+    const int n = w->n_dofs;
+    auto at = [&](auto *p) { return p ? p + done * n : nullptr; };
+    auto go = [&](auto kernel) {
+        int rc = ensure_lds(kernel, g.lds_bytes);
+        if (rc) return rc;
+        hipLaunchKernelGGL(kernel, g.grid, g.block, g.lds_bytes, c.s, w->ops_f, w->ops_i, (int)w->capacity, (int)w->n_ops,
+                           (int)DRM_WALK_LEAVES(w->shape), n, (int)w->n_slots, c.flags, c.q + done * n, c.qd + done * n, at(c.qdd),
+                           c.grad_tau + done * n, c.B - done, at(c.grad_q), at(c.grad_qd), at(c.grad_qdd), c.param_mask, prow, park, div_magic(n),
+                           g.lds_per_wave, align);
+        return launched();
+    };
+    return hbm ? go(rnea_backward_kernel<true>) : go(rnea_backward_kernel<false>);
+}
+
+// what a rung that took the full tiles does when the ragged tail's records do not fit LDS
+enum TailRecords {
+    TAIL_PARKS_IN_HBM, // behind the rows of partial sums (the walk's own kernel: any walk)
+    TAIL_FITS_LDS,     // not asked (7-DoF arms: always fit)
+    TAIL_MUST_FIT_LDS  // DRM_ERR_UNSUPPORTED (hands, arms that carry a hand)
+};
+// The ragged tail, rows [done, B) with B - done < 64, on one wavefront of the loop kernel; its row of partial sums is appended
+// to the `rows` the full tiles wrote.
+static int rnea_backward_tail(const RneaBackwardCall &c, int64_t done, int &rows, TailRecords records) {
+    const drm_walk *w = c.w;
+    const bool over = rnea_backward_lds_floats(w, false) * sizeof(float) > (size_t)MAX_LDS_BYTES;
+    if (over && records == TAIL_MUST_FIT_LDS) return fail(DRM_ERR_UNSUPPORTED, "the tail of this walk does not fit LDS");
+    const bool park_tail = over && records == TAIL_PARKS_IN_HBM; // (one wavefront's records behind the rows of partial sums)
+    Geometry gt;
+    int rc = make_geometry(c.B - done, (int)rnea_backward_lds_floats(w, park_tail), gt);
+    if (rc) return rc;
+    gt.grid = dim3(1);
+    gt.block = dim3(WAVE);
+    gt.lds_bytes = (size_t)gt.lds_per_wave * sizeof(float);
+    const int64_t row_floats = (int64_t)w->capacity * DRM_OPF_STRIDE;
+    float *park = records == TAIL_PARKS_IN_HBM ? c.partials + (rows + 1) * row_floats : nullptr;
+    // (the gradients' alignment bits stay clear: the tail's rows start anywhere)
+    const uint32_t al = al16(c.q, AL_Q) | al16(c.qd, AL_QD) | al16(c.qdd, AL_QDD) | al16(c.grad_tau, AL_TAU);
+    rc = launch_rnea_backward_loop(c, gt, done, c.partials + rows * row_floats, park, al, park_tail);
+    if (rc) return rc;
+    rows += 1;
+    return DRM_OK;
+}
+
+// grad_ops_f (when asked for) = the sum of the `rows` rows of partial sums
+static int rnea_backward_reduce(const RneaBackwardCall &c, int rows) {
+    if (!c.grad_ops_f) return DRM_OK;
+    const int cap = c.w->capacity;
+    hipLaunchKernelGGL(rnea_backward_reduce_kernel, dim3((unsigned)(cap * DRM_OPF_STRIDE / WAVE)), dim3(WAVE * REDUCE_WAVES), 0, c.s, c.partials,
+                       rows, cap, c.grad_ops_f);
+    return launched();
+}
+
+// the ragged tail (if any) behind full tiles that are already launched, then the reduction
+static int rnea_backward_finish(const RneaBackwardCall &c, int64_t done, int rows, TailRecords records) {
+    if (done < c.B) {
+        int rc = rnea_backward_tail(c, done, rows, records);
+        if (rc) return rc;
+    }
+    return rnea_backward_reduce(c, rows);
+}
+
+#ifndef DRM_NO_ARM_KERNEL
+// 7-DoF arms with every pointer 16-byte aligned: full tiles through the chain kernels, the ragged tail (if any) through the generic
+// one with its own row of partial sums appended after the chain kernel's.  `taken` = the call is answered.
+static int rnea_backward_arm(const RneaBackwardCall &c, bool &taken) {
+    const drm_walk *w = c.w;
+    const int n = w->n_dofs;
+    const int64_t B = c.B;
+    taken = arm7_walk(w) && aligned16(c.q, c.qd, c.qdd, c.grad_tau, c.grad_q, c.grad_qd, c.grad_qdd, w->ops_f) && full_tiles_fit(B);
+    if (!taken) return DRM_OK;
+    int n_tiles = (int)(B / WAVE), fl = c.flags;
+    const int64_t done = (int64_t)n_tiles * WAVE;
+    const bool inputs_only = c.param_mask == 0 && c.grad_q != nullptr;
+    // (the input gradients only: rows [from, B) re-enter with `rest`, the walk with that rung switched off)
+    auto tail = [&](int64_t from, const drm_walk &rest) {
+        return drm_rnea_backward(&rest, c.q + from * n, c.qd + from * n, c.qdd ? c.qdd + from * n : nullptr, B - from, c.flags,
+                                 c.grad_tau + from * n, c.param_mask, c.grad_q + from * n, c.grad_qd + from * n, c.grad_qdd + from * n,
+                                 c.grad_ops_f, c.partials, (void *)c.s);
+    };
+    if (w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM2] && w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM] && inputs_only &&
+        n_tiles / 2 >= DRM_ARM_STATIC_MIN_PAIRS) {
+        // ABI 11: two samples per lane for the pairs of tiles of a large launch; an odd tile and the tail follow below
+        int n_pairs = n_tiles / 2;
+        int rc = launch_module(w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM2], (unsigned)n_pairs, WAVE, c.s, "drm_rnea_backward_arm2_static", c.q, c.qd,
+                               c.qdd, c.grad_tau, n_pairs, fl, c.grad_q, c.grad_qd, c.grad_qdd);
+        const int64_t done2 = (int64_t)n_pairs * 2 * WAVE;
+        return rc || done2 == B ? rc : tail(done2, without_special(*w, DRM_SPECIAL_RNEA_BACKWARD_ARM2));
+    }
+    if (w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM] && inputs_only) {
+        // input gradients of a constant model through this arm's own kernel, its constants folded into the instruction
+        // stream (csrc/drm_arm_static.hpp, specialize.py): nothing is summed over the batch, so no partial rows
+        int rc = launch_module(w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM], (unsigned)n_tiles, WAVE, c.s, "drm_rnea_backward_arm_static", c.q, c.qd,
+                               c.qdd, c.grad_tau, n_tiles, fl, c.grad_q, c.grad_qd, c.grad_qdd);
+        return rc || done == B ? rc : tail(done, without_special(*w, DRM_SPECIAL_RNEA_BACKWARD_ARM));
+    }
+    const int waves_a = backward_waves(done, MAX_WAVES_PER_BLOCK);
+    const dim3 grid((unsigned)(waves_a / MAX_WAVES_PER_BLOCK)), block(WAVE * MAX_WAVES_PER_BLOCK);
+    if (w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM_PARAM] && c.param_mask != 0 && c.param_mask == (uint64_t)w->reserved0) {
+        // ABI 11: this arm's own reverse-mode kernel for exactly this set of learnable blocks (csrc/drm_arm_static.hpp
+        // rnea_backward_arm_param_static_body, specialize.py): the constant blocks of the table folded into the instruction
+        // stream, the learnable ones read from ops_f; same rows of partial sums, same reduction below
+        int rc = launch_module(w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM_PARAM], grid.x, block.x, c.s, "drm_rnea_backward_arm_param_static", w->ops_f,
+                               c.q, c.qd, c.qdd, c.grad_tau, n_tiles, fl, c.grad_q, c.grad_qd, c.grad_qdd, c.partials);
+        if (rc) return rc;
+    } else if (arm_links(w) == 7)
+        hipLaunchKernelGGL((rnea_backward_arm_kernel<8, 7, 7>), grid, block, 0, c.s, w->ops_f, c.q, c.qd, c.qdd, c.grad_tau, n_tiles, c.flags,
+                           c.param_mask, c.grad_q, c.grad_qd, c.grad_qdd, c.partials);
+    else
+        hipLaunchKernelGGL((rnea_backward_arm_kernel<8, 7, 8>), grid, block, 0, c.s, w->ops_f, c.q, c.qd, c.qdd, c.grad_tau, n_tiles, c.flags,
+                           c.param_mask, c.grad_q, c.grad_qd, c.grad_qdd, c.partials);
+    int rc = launched();
+    if (rc) return rc;
+    // (tail: < 64 rows, one wave, through the generic kernel — LDS parking: an arm always fits)
+    return rnea_backward_finish(c, done, waves_a, TAIL_FITS_LDS);
+}
+#endif
+
+#ifndef DRM_NO_FINGERS_KERNEL
+// a hand (DRM_WALK_FINGERS): full tiles through the per-finger kernel; rows covered (0: not this walk), `rows` its partial sums
+static int launch_rnea_backward_fingers(const RneaBackwardCall &c, int64_t &done, int &rows) {
+    const drm_walk *w = c.w;
+    int K, L;
+    if (!(w->shape & DRM_WALK_FINGERS) || !full_tiles_fit(c.B) || !table_aligned(w) || !fingers_shape(w, K, L) || w->capacity < w->n_ops)
+        return DRM_OK;
+    const int n = w->n_dofs, cap = w->capacity, n_tiles = (int)(c.B / WAVE);
+    int resident = 0;
+    int rc = L == 2 ? resident_blocks(rnea_backward_fingers_kernel<2>, WAVE * K, 0, resident)
+                    : L == 3 ? resident_blocks(rnea_backward_fingers_kernel<3>, WAVE * K, 0, resident)
+                             : resident_blocks(rnea_backward_fingers_kernel<4>, WAVE * K, 0, resident);
+    if (rc) return rc;
+    if (resident > BWD_MAX_WAVES) resident = BWD_MAX_WAVES;
+    const int grid = n_tiles < resident ? n_tiles : resident;
+    const int vec = (n % 4 == 0) && aligned16(c.q, c.qd, c.qdd, c.grad_tau, c.grad_q, c.grad_qd, c.grad_qdd);
+#define X(l)                                                                                                                    \
+    if (L == l)                                                                                                                  \
+        hipLaunchKernelGGL((rnea_backward_fingers_kernel<l>), dim3((unsigned)grid), dim3(WAVE * K), 0, c.s, w->ops_f, c.q, c.qd, c.qdd, \
+                           c.grad_tau, n, cap, n_tiles, c.flags, c.param_mask, c.grad_q, c.grad_qd, c.grad_qdd, c.partials, vec);
+    X(2) X(3) X(4)
+#undef X
+    rows = grid;
+    done = (int64_t)n_tiles * WAVE;
+    return DRM_OK;
+}
+#endif
+
+// fanned out over the segments, one wavefront each: when the walk has several, none of the prefix ops is learnable and a block's
+// LDS fits.  `taken` = it ran (with its reduction).
+static int rnea_backward_fan(const RneaBackwardCall &c, bool &taken) {
+    const drm_walk *w = c.w;
+    const int n = w->n_dofs, cap = w->capacity, n_leaves = DRM_WALK_LEAVES(w->shape);
+    taken = false;
+    if (!(w->n_segments > 1 && segments_ok(w) && w->prefix_end < 64 && !(c.param_mask & ((1ull << w->prefix_end) - 1ull)))) return DRM_OK;
+    FanArgs fa;
+    fa.n_seg = w->n_segments; fa.p_end = w->prefix_end;
+    const size_t shared = (size_t)4 * round4(WAVE * pad_odd(n)) + (size_t)w->n_slots * SLOT_FLOATS * WAVE;
+    size_t off = shared;
+    bool ok = true;
+    for (int sgm = 0; sgm <= DRM_MAX_SEGMENTS; ++sgm) {
+        fa.seg_begin[sgm] = sgm <= w->n_segments ? w->seg_begin[sgm] : w->n_ops;
+        fa.leaf_begin[sgm] = sgm <= w->n_segments ? w->seg_leaf_begin[sgm] : n_leaves;
+    }
+    for (int sgm = 0; sgm < DRM_MAX_SEGMENTS; ++sgm) {
+        fa.wave_off[sgm] = (int32_t)off;
+        if (sgm < w->n_segments) {
+            const int ops_s = fa.seg_begin[sgm + 1] - fa.seg_begin[sgm], leaves_s = fa.leaf_begin[sgm + 1] - fa.leaf_begin[sgm];
+            if (ops_s < 0 || leaves_s < 0 || leaves_s > ops_s) ok = false;
+            off += (size_t)round4(cap * DRM_OPF_STRIDE + record_floats(ops_s, leaves_s));
+        }
+    }
+    const size_t lds_bytes = off * sizeof(float);
+    if (!ok || lds_bytes > (size_t)MAX_LDS_BYTES) return DRM_OK;
+    const int64_t tiles = (c.B + WAVE - 1) / WAVE;
+    int64_t blocks = BWD_MAX_WAVES / w->n_segments;
+    if (blocks > tiles) blocks = tiles;
+    int rc = ensure_lds(rnea_backward_fan_kernel, lds_bytes);
+    if (rc) return rc;
+    const uint32_t al = al16(c.q, AL_Q) | al16(c.qd, AL_QD) | al16(c.qdd, AL_QDD) | al16(c.grad_tau, AL_TAU) |
+                        al16(c.grad_q, AL_POS) | al16(c.grad_qd, AL_QUAT) | al16(c.grad_qdd, AL_LIN);
+    hipLaunchKernelGGL(rnea_backward_fan_kernel, dim3((unsigned)blocks), dim3((unsigned)(WAVE * w->n_segments)), lds_bytes, c.s,
+                       w->ops_f, w->ops_i, fa, cap, n, (int)w->n_slots, c.flags, c.q, c.qd, c.qdd, c.grad_tau, c.B, c.grad_q, c.grad_qd,
+                       c.grad_qdd, c.param_mask, c.partials, div_magic(n), al);
+    rc = launched();
+    if (rc) return rc;
+    taken = true;
+    return rnea_backward_reduce(c, (int)(blocks * w->n_segments));
+}
+
 extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B,
                                  int32_t flags, const float *grad_tau, uint64_t param_mask, float *grad_q, float *grad_qd,
                                  float *grad_qdd, float *grad_ops_f, float *scratch, void *stream) {
@@ -488,7 +695,7 @@ extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float 
     if (!want_q && !grad_ops_f) return fail(DRM_ERR_INVALID, "nothing to compute");
     if (!scratch) return fail(DRM_ERR_INVALID, "scratch must not be NULL (drm_rnea_backward_scratch_floats)");
     if (w->capacity < 64 && (param_mask >> w->capacity)) return fail(DRM_ERR_INVALID, "param_mask selects ops beyond the walk's capacity");
-    const int n = w->n_dofs, cap = w->capacity, n_leaves = DRM_WALK_LEAVES(w->shape);
+    const int cap = w->capacity, n_leaves = DRM_WALK_LEAVES(w->shape);
     if (w->n_ops > 0 && (n_leaves < 1 || n_leaves > w->n_ops || n_leaves > 64))
         return fail(DRM_ERR_INVALID, "walk without its leaf count (drm_walk.shape bits 16..23; host built for an older ABI?)");
     hipStream_t s = (hipStream_t)stream;
@@ -500,148 +707,26 @@ extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float 
         return DRM_OK;
     }
     float *partials = scratch;
-    if (w->special[DRM_SPECIAL_RNEA_BACKWARD] && B >= WAVE && B / WAVE < 0x7fffffffLL && (((uintptr_t)w->ops_f) & 15u) == 0) {
+    const RneaBackwardCall call = {w, q, qd, qdd, grad_tau, B, (int)flags, param_mask, grad_q, grad_qd, grad_qdd, grad_ops_f, partials, s};
+    if (w->special[DRM_SPECIAL_RNEA_BACKWARD] && full_tiles_fit(B) && table_aligned(w)) {
         // a per-robot straight-line kernel built for exactly this walk (csrc/drm_static.hpp, specialize.py): full tiles on as many
         // wavefronts as the device holds at once, any pointer alignment; the ragged tail through the loop kernel, its row of
         // partial sums appended
-        hipFunction_t fn = (hipFunction_t)w->special[DRM_SPECIAL_RNEA_BACKWARD];
+        const void *fn = w->special[DRM_SPECIAL_RNEA_BACKWARD];
         int n_tiles = (int)(B / WAVE), fl = (int)flags, grid = 0;
-        rc = resident_blocks_module(fn, WAVE, grid);
+        rc = resident_blocks_module((hipFunction_t)fn, WAVE, grid);
         if (rc) return rc;
         if (grid > BWD_MAX_WAVES) grid = BWD_MAX_WAVES;
         if (grid > n_tiles) grid = n_tiles;
-        void *args[] = {(void *)&w->ops_f, (void *)&q, (void *)&qd, (void *)&qdd, (void *)&grad_tau, (void *)&n_tiles, (void *)&fl,
-                        (void *)&param_mask, (void *)&grad_q, (void *)&grad_qd, (void *)&grad_qdd, (void *)&partials};
-        hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-        if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_rnea_backward_static): %s", hipGetErrorString(e));
-        int rows = grid;
-        const int64_t done = (int64_t)n_tiles * WAVE;
-        if (done < B) {
-            const size_t need = rnea_backward_lds_floats(n, w->n_slots, cap, w->n_ops, n_leaves, false) * sizeof(float);
-            const bool park_tail = need > (size_t)MAX_LDS_BYTES; // (one wavefront's records behind the rows of partial sums)
-            Geometry gt;
-            rc = make_geometry(B - done, (int)rnea_backward_lds_floats(n, w->n_slots, cap, w->n_ops, n_leaves, park_tail), gt);
-            if (rc) return rc;
-            gt.grid = dim3(1);
-            gt.block = dim3(WAVE);
-            gt.lds_bytes = (size_t)gt.lds_per_wave * sizeof(float);
-            const uint32_t al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(grad_tau, AL_TAU);
-            float *park = partials + (int64_t)(rows + 1) * cap * DRM_OPF_STRIDE;
-#define DRM_LAUNCH_TAIL(HBM)                                                                                                     \
-    {                                                                                                                            \
-        rc = ensure_lds(rnea_backward_kernel<HBM>, gt.lds_bytes);                                                                \
-        if (rc) return rc;                                                                                                       \
-        hipLaunchKernelGGL((rnea_backward_kernel<HBM>), gt.grid, gt.block, gt.lds_bytes, s, w->ops_f, w->ops_i, cap, (int)w->n_ops, \
-                           n_leaves, n, (int)w->n_slots, (int)flags, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr,   \
-                           grad_tau + done * n, B - done, grad_q ? grad_q + done * n : nullptr,                                   \
-                           grad_qd ? grad_qd + done * n : nullptr, grad_qdd ? grad_qdd + done * n : nullptr, param_mask,           \
-                           partials + (int64_t)rows * cap * DRM_OPF_STRIDE, park, div_magic(n), gt.lds_per_wave,                   \
-                           al & ~(AL_POS | AL_QUAT | AL_LIN));                                                                    \
-    }
-            if (park_tail) DRM_LAUNCH_TAIL(true) else DRM_LAUNCH_TAIL(false)
-#undef DRM_LAUNCH_TAIL
-            rc = launched();
-            if (rc) return rc;
-            rows += 1;
-        }
-        if (grad_ops_f) {
-            hipLaunchKernelGGL(rnea_backward_reduce_kernel, dim3((unsigned)(cap * DRM_OPF_STRIDE / WAVE)), dim3(WAVE * REDUCE_WAVES), 0, s,
-                               partials, rows, cap, grad_ops_f);
-            rc = launched();
-        }
-        return rc;
+        rc = launch_module(fn, (unsigned)grid, WAVE, s, "drm_rnea_backward_static", w->ops_f, q, qd, qdd, grad_tau, n_tiles, fl, param_mask, grad_q,
+                           grad_qd, grad_qdd, partials);
+        if (rc) return rc;
+        return rnea_backward_finish(call, (int64_t)n_tiles * WAVE, grid, TAIL_PARKS_IN_HBM);
     }
 #ifndef DRM_NO_ARM_KERNEL
-    {
-        const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)qd | (uintptr_t)qdd | (uintptr_t)grad_tau | (uintptr_t)grad_q |
-                               (uintptr_t)grad_qd | (uintptr_t)grad_qdd | (uintptr_t)w->ops_f;
-        if ((w->shape & DRM_WALK_ARM_CHAIN) && cap == 8 && n == 7 && (ptrs & 15u) == 0 && B >= WAVE &&
-            B / WAVE < 0x7fffffffLL) {
-            // 7-DoF arms: full tiles through the chain kernel, the ragged tail (if any) through the generic one with
-            // its own rows of partial sums appended after the chain kernel's
-            int n_tiles = (int)(B / WAVE);
-            const int64_t done = (int64_t)n_tiles * WAVE;
-            if (w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM2] && w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM] && param_mask == 0 && want_q &&
-                n_tiles / 2 >= DRM_ARM_STATIC_MIN_PAIRS) {
-                // ABI 11: two samples per lane for the pairs of tiles of a large launch; an odd tile and the tail follow below
-                int n_pairs = n_tiles / 2, fl = (int)flags;
-                void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&grad_tau, (void *)&n_pairs, (void *)&fl,
-                                (void *)&grad_q, (void *)&grad_qd, (void *)&grad_qdd};
-                hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM2], (unsigned)n_pairs, 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-                if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_rnea_backward_arm2_static): %s", hipGetErrorString(e));
-                const int64_t done2 = (int64_t)n_pairs * 2 * WAVE;
-                if (done2 == B) return DRM_OK;
-                drm_walk rest = *w;
-                rest.special[DRM_SPECIAL_RNEA_BACKWARD_ARM2] = nullptr;
-                return drm_rnea_backward(&rest, q + done2 * n, qd + done2 * n, qdd ? qdd + done2 * n : nullptr, B - done2, flags, grad_tau + done2 * n,
-                                         param_mask, grad_q + done2 * n, grad_qd + done2 * n, grad_qdd + done2 * n, grad_ops_f, scratch, stream);
-            }
-            if (w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM] && param_mask == 0 && want_q) {
-                // input gradients of a constant model through this arm's own kernel, its constants folded into the instruction
-                // stream (csrc/drm_arm_static.hpp, specialize.py): nothing is summed over the batch, so no partial rows
-                int fl = (int)flags;
-                void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&grad_tau, (void *)&n_tiles, (void *)&fl,
-                                (void *)&grad_q, (void *)&grad_qd, (void *)&grad_qdd};
-                hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM], (unsigned)n_tiles, 1, 1, WAVE, 1, 1, 0, s, args, nullptr);
-                if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_rnea_backward_arm_static): %s", hipGetErrorString(e));
-                if (done == B) return DRM_OK;
-                drm_walk rest = *w;
-                rest.special[DRM_SPECIAL_RNEA_BACKWARD_ARM] = nullptr;
-                return drm_rnea_backward(&rest, q + done * n, qd + done * n, qdd ? qdd + done * n : nullptr, B - done, flags, grad_tau + done * n,
-                                         param_mask, grad_q + done * n, grad_qd + done * n, grad_qdd + done * n, grad_ops_f, scratch, stream);
-            }
-            const int waves_a = backward_waves(done, MAX_WAVES_PER_BLOCK);
-            if (w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM_PARAM] && param_mask != 0 && param_mask == (uint64_t)w->reserved0) {
-                // ABI 11: this arm's own reverse-mode kernel for exactly this set of learnable blocks (csrc/drm_arm_static.hpp
-                // rnea_backward_arm_param_static_body, specialize.py): the constant blocks of the table folded into the instruction
-                // stream, the learnable ones read from ops_f; same rows of partial sums, same reduction below
-                int fl = (int)flags;
-                void *args[] = {(void *)&w->ops_f, (void *)&q, (void *)&qd, (void *)&qdd, (void *)&grad_tau, (void *)&n_tiles, (void *)&fl,
-                                (void *)&grad_q, (void *)&grad_qd, (void *)&grad_qdd, (void *)&partials};
-                hipError_t e = hipModuleLaunchKernel((hipFunction_t)w->special[DRM_SPECIAL_RNEA_BACKWARD_ARM_PARAM],
-                                                     (unsigned)(waves_a / MAX_WAVES_PER_BLOCK), 1, 1, WAVE * MAX_WAVES_PER_BLOCK, 1, 1, 0, s, args, nullptr);
-                if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipModuleLaunchKernel(drm_rnea_backward_arm_param_static): %s", hipGetErrorString(e));
-            } else if (arm_links(w) == 7)
-                hipLaunchKernelGGL((rnea_backward_arm_kernel<8, 7, 7>), dim3((unsigned)(waves_a / MAX_WAVES_PER_BLOCK)),
-                                   dim3(WAVE * MAX_WAVES_PER_BLOCK), 0, s, w->ops_f, q, qd, qdd, grad_tau, n_tiles, (int)flags,
-                                   param_mask, grad_q, grad_qd, grad_qdd, partials);
-            else
-                hipLaunchKernelGGL((rnea_backward_arm_kernel<8, 7, 8>), dim3((unsigned)(waves_a / MAX_WAVES_PER_BLOCK)),
-                                   dim3(WAVE * MAX_WAVES_PER_BLOCK), 0, s, w->ops_f, q, qd, qdd, grad_tau, n_tiles, (int)flags,
-                                   param_mask, grad_q, grad_qd, grad_qdd, partials);
-            rc = launched();
-            if (rc) return rc;
-            int rows = waves_a;
-            if (done < B) {
-                // tail: < 64 rows, one wave, through the generic kernel (LDS parking: an arm always fits)
-                Geometry gt;
-                rc = make_geometry(B - done, (int)rnea_backward_lds_floats(n, w->n_slots, cap, w->n_ops, n_leaves, false), gt);
-                if (rc) return rc;
-                gt.grid = dim3(1);
-                gt.block = dim3(WAVE);
-                gt.lds_bytes = (size_t)gt.lds_per_wave * sizeof(float);
-                rc = ensure_lds(rnea_backward_kernel<false>, gt.lds_bytes);
-                if (rc) return rc;
-                const uint32_t al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(grad_tau, AL_TAU);
-                hipLaunchKernelGGL((rnea_backward_kernel<false>), gt.grid, gt.block, gt.lds_bytes, s, w->ops_f, w->ops_i,
-                                   cap, (int)w->n_ops, n_leaves, n, (int)w->n_slots, (int)flags, q + done * n, qd + done * n,
-                                   qdd ? qdd + done * n : nullptr, grad_tau + done * n, B - done,
-                                   grad_q ? grad_q + done * n : nullptr, grad_qd ? grad_qd + done * n : nullptr,
-                                   grad_qdd ? grad_qdd + done * n : nullptr, param_mask,
-                                   partials + (int64_t)waves_a * cap * DRM_OPF_STRIDE, (float *)nullptr, div_magic(n),
-                                   gt.lds_per_wave, al & ~(AL_POS | AL_QUAT | AL_LIN));
-                rc = launched();
-                if (rc) return rc;
-                rows += 1;
-            }
-            if (grad_ops_f) {
-                hipLaunchKernelGGL(rnea_backward_reduce_kernel, dim3((unsigned)(cap * DRM_OPF_STRIDE / WAVE)), dim3(WAVE * REDUCE_WAVES), 0, s, partials, rows, cap,
-                                   grad_ops_f);
-                rc = launched();
-            }
-            return rc;
-        }
-    }
+    bool arm;
+    rc = rnea_backward_arm(call, arm);
+    if (rc || arm) return rc;
 #endif
     {   // a hand (DRM_WALK_FINGERS) / an arm that carries a hand (Panda with gripper, Jaco, iiwa7 + Allegro): full tiles through
         // the straight-line kernels, the ragged tail (< 64 rows, one wavefront) through the loop kernel with its row of partial
@@ -649,29 +734,8 @@ extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float 
         int rows = 0;
         int64_t done = 0;
 #ifndef DRM_NO_FINGERS_KERNEL
-        if ((w->shape & DRM_WALK_FINGERS) && B >= WAVE && B / WAVE < 0x7fffffffLL && (((uintptr_t)w->ops_f) & 15u) == 0) {
-            const int K = DRM_WALK_AH_K(w->shape), L = DRM_WALK_AH_L(w->shape);
-            if (K * L == w->n_ops && n == w->n_ops && K >= 2 && K <= 4 && L >= 2 && L <= 4 && cap >= w->n_ops) {
-                const int n_tiles = (int)(B / WAVE);
-                int resident = 0;
-                rc = L == 2 ? resident_blocks(rnea_backward_fingers_kernel<2>, WAVE * K, 0, resident)
-                            : L == 3 ? resident_blocks(rnea_backward_fingers_kernel<3>, WAVE * K, 0, resident)
-                                     : resident_blocks(rnea_backward_fingers_kernel<4>, WAVE * K, 0, resident);
-                if (rc) return rc;
-                if (resident > BWD_MAX_WAVES) resident = BWD_MAX_WAVES;
-                const int grid = n_tiles < resident ? n_tiles : resident;
-                const int vec = (n % 4 == 0) && ((((uintptr_t)q | (uintptr_t)qd | (uintptr_t)qdd | (uintptr_t)grad_tau | (uintptr_t)grad_q |
-                                                   (uintptr_t)grad_qd | (uintptr_t)grad_qdd) & 15u) == 0);
-#define X(l)                                                                                                                    \
-    if (L == l)                                                                                                                  \
-        hipLaunchKernelGGL((rnea_backward_fingers_kernel<l>), dim3((unsigned)grid), dim3(WAVE * K), 0, s, w->ops_f, q, qd, qdd,    \
-                           grad_tau, n, cap, n_tiles, (int)flags, param_mask, grad_q, grad_qd, grad_qdd, partials, vec);
-                X(2) X(3) X(4)
-#undef X
-                rows = grid;
-                done = (int64_t)n_tiles * WAVE;
-            }
-        }
+        rc = launch_rnea_backward_fingers(call, done, rows);
+        if (rc) return rc;
 #endif
         if (done == 0)
             done = launch_rnea_backward_arm_hand(w, q, qd, qdd, grad_tau, B, (int)flags, param_mask, grad_q, grad_qd, grad_qdd,
@@ -679,82 +743,15 @@ extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float 
         if (done > 0) {
             rc = launched();
             if (rc) return rc;
-            if (done < B) {
-                const size_t need = rnea_backward_lds_floats(n, w->n_slots, cap, w->n_ops, n_leaves, false) * sizeof(float);
-                if (need > (size_t)MAX_LDS_BYTES) return fail(DRM_ERR_UNSUPPORTED, "the tail of this walk does not fit LDS");
-                Geometry gt;
-                rc = make_geometry(B - done, (int)(need / sizeof(float)), gt);
-                if (rc) return rc;
-                gt.grid = dim3(1);
-                gt.block = dim3(WAVE);
-                gt.lds_bytes = (size_t)gt.lds_per_wave * sizeof(float);
-                rc = ensure_lds(rnea_backward_kernel<false>, gt.lds_bytes);
-                if (rc) return rc;
-                const uint32_t al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(grad_tau, AL_TAU);
-                hipLaunchKernelGGL((rnea_backward_kernel<false>), gt.grid, gt.block, gt.lds_bytes, s, w->ops_f, w->ops_i, cap,
-                                   (int)w->n_ops, n_leaves, n, (int)w->n_slots, (int)flags, q + done * n, qd + done * n,
-                                   qdd ? qdd + done * n : nullptr, grad_tau + done * n, B - done,
-                                   grad_q ? grad_q + done * n : nullptr, grad_qd ? grad_qd + done * n : nullptr,
-                                   grad_qdd ? grad_qdd + done * n : nullptr, param_mask,
-                                   partials + (int64_t)rows * cap * DRM_OPF_STRIDE, (float *)nullptr, div_magic(n), gt.lds_per_wave,
-                                   al & ~(AL_POS | AL_QUAT | AL_LIN));
-                rc = launched();
-                if (rc) return rc;
-                rows += 1;
-            }
-            if (grad_ops_f) {
-                hipLaunchKernelGGL(rnea_backward_reduce_kernel, dim3((unsigned)(cap * DRM_OPF_STRIDE / WAVE)), dim3(WAVE * REDUCE_WAVES), 0, s,
-                                   partials, rows, cap, grad_ops_f);
-                rc = launched();
-            }
-            return rc;
+            return rnea_backward_finish(call, done, rows, TAIL_MUST_FIT_LDS);
         }
     }
-    // fanned out over the segments when the walk has several, none of the prefix ops is learnable and a block's LDS fits twice
-    // per CU or better than the single-wavefront form would
-    if (w->n_segments > 1 && segments_ok(w) && w->prefix_end < 64 && !(param_mask & ((1ull << w->prefix_end) - 1ull))) {
-        FanArgs fa;
-        fa.n_seg = w->n_segments; fa.p_end = w->prefix_end;
-        const size_t shared = (size_t)4 * round4(WAVE * pad_odd(n)) + (size_t)w->n_slots * SLOT_FLOATS * WAVE;
-        size_t off = shared;
-        bool ok = true;
-        for (int sgm = 0; sgm <= DRM_MAX_SEGMENTS; ++sgm) {
-            fa.seg_begin[sgm] = sgm <= w->n_segments ? w->seg_begin[sgm] : w->n_ops;
-            fa.leaf_begin[sgm] = sgm <= w->n_segments ? w->seg_leaf_begin[sgm] : n_leaves;
-        }
-        for (int sgm = 0; sgm < DRM_MAX_SEGMENTS; ++sgm) {
-            fa.wave_off[sgm] = (int32_t)off;
-            if (sgm < w->n_segments) {
-                const int ops_s = fa.seg_begin[sgm + 1] - fa.seg_begin[sgm], leaves_s = fa.leaf_begin[sgm + 1] - fa.leaf_begin[sgm];
-                if (ops_s < 0 || leaves_s < 0 || leaves_s > ops_s) ok = false;
-                off += (size_t)round4(cap * DRM_OPF_STRIDE + record_floats(ops_s, leaves_s));
-            }
-        }
-        const size_t lds_bytes = off * sizeof(float);
-        if (ok && lds_bytes <= (size_t)MAX_LDS_BYTES) {
-            const int64_t tiles = (B + WAVE - 1) / WAVE;
-            int64_t blocks = BWD_MAX_WAVES / w->n_segments;
-            if (blocks > tiles) blocks = tiles;
-            rc = ensure_lds(rnea_backward_fan_kernel, lds_bytes);
-            if (rc) return rc;
-            const uint32_t al = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(grad_tau, AL_TAU) |
-                                al16(grad_q, AL_POS) | al16(grad_qd, AL_QUAT) | al16(grad_qdd, AL_LIN);
-            hipLaunchKernelGGL(rnea_backward_fan_kernel, dim3((unsigned)blocks), dim3((unsigned)(WAVE * w->n_segments)), lds_bytes, s,
-                               w->ops_f, w->ops_i, fa, cap, n, (int)w->n_slots, (int)flags, q, qd, qdd, grad_tau, B, grad_q, grad_qd,
-                               grad_qdd, param_mask, partials, div_magic(n), al);
-            rc = launched();
-            if (rc) return rc;
-            if (grad_ops_f) {
-                hipLaunchKernelGGL(rnea_backward_reduce_kernel, dim3((unsigned)(cap * DRM_OPF_STRIDE / WAVE)), dim3(WAVE * REDUCE_WAVES), 0, s,
-                                   partials, (int)(blocks * w->n_segments), cap, grad_ops_f);
-                rc = launched();
-            }
-            return rc;
-        }
-    }
-    const bool park_hbm = rnea_backward_lds_floats(n, w->n_slots, cap, w->n_ops, n_leaves, false) * sizeof(float) > (size_t)MAX_LDS_BYTES;
+    bool fanned;
+    rc = rnea_backward_fan(call, fanned);
+    if (rc || fanned) return rc;
+    const bool park_hbm = rnea_backward_lds_floats(w, false) * sizeof(float) > (size_t)MAX_LDS_BYTES;
     Geometry g;
-    rc = make_geometry(B, (int)rnea_backward_lds_floats(n, w->n_slots, cap, w->n_ops, n_leaves, park_hbm), g);
+    rc = make_geometry(B, (int)rnea_backward_lds_floats(w, park_hbm), g);
     if (rc) return rc;
     const int wpb = (int)(g.block.x / WAVE);
     const int waves = backward_waves(B, wpb);
@@ -768,22 +765,7 @@ extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float 
     }
     const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(grad_tau, AL_TAU) |
                            al16(grad_q, AL_POS) | al16(grad_qd, AL_QUAT) | al16(grad_qdd, AL_LIN);
-#define DRM_LAUNCH_RB(HBM)                                                                                             \
-    {                                                                                                                  \
-        rc = ensure_lds(rnea_backward_kernel<HBM>, g.lds_bytes);                                                       \
-        if (rc) return rc;                                                                                             \
-        hipLaunchKernelGGL((rnea_backward_kernel<HBM>), g.grid, g.block, g.lds_bytes, s, w->ops_f, w->ops_i, cap,      \
-                           (int)w->n_ops, n_leaves, n, (int)w->n_slots, (int)flags, q, qd, qdd, grad_tau, B, grad_q, grad_qd,    \
-                           grad_qdd, param_mask, partials, park, div_magic(n), g.lds_per_wave, align);                 \
-    }
-    if (park_hbm) DRM_LAUNCH_RB(true) else DRM_LAUNCH_RB(false)
-#undef DRM_LAUNCH_RB
-    rc = launched();
+    rc = launch_rnea_backward_loop(call, g, 0, partials, park, align, park_hbm);
     if (rc) return rc;
-    if (grad_ops_f) {
-        hipLaunchKernelGGL(rnea_backward_reduce_kernel, dim3((unsigned)(cap * DRM_OPF_STRIDE / WAVE)), dim3(WAVE * REDUCE_WAVES), 0, s, partials, waves, cap,
-                           grad_ops_f);
-        rc = launched();
-    }
-    return rc;
+    return rnea_backward_reduce(call, waves);
 }

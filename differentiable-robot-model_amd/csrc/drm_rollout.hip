@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "drm_common.hpp"
+#include "drm_dispatch.hpp"
 #include "drm_rollout.hpp"
 #include "drm_sample.hpp"
 
@@ -227,13 +228,12 @@ enum RolloutKind { ROLLOUT_COMPOSED = 0, ROLLOUT_ARM = 1, ROLLOUT_FINGERS = 2 };
 
 // which fused kernel takes the full tiles of this walk (ROLLOUT_COMPOSED: none); `aligned`: every pointer is 16-byte aligned
 static RolloutKind rollout_kind(const drm_walk *w, int64_t B, bool aligned) {
-    if (B < WAVE || B / WAVE >= 0x7fffffffLL || (((uintptr_t)w->ops_f) & 15u) != 0) return ROLLOUT_COMPOSED;
-    const int n = w->n_dofs;
+    if (!full_tiles_fit(B) || !table_aligned(w)) return ROLLOUT_COMPOSED;
     if ((w->shape & DRM_WALK_FINGERS)) {
-        const int K = DRM_WALK_AH_K(w->shape), L = DRM_WALK_AH_L(w->shape);
-        if (K * L == w->n_ops && n == w->n_ops && K >= 2 && K <= 4 && L >= 2 && L <= 4) return ROLLOUT_FINGERS;
+        int K, L;
+        if (fingers_shape(w, K, L)) return ROLLOUT_FINGERS;
     }
-    if ((w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && n == 7 && aligned) {
+    if (arm7_walk(w) && aligned) {
         // an arm whose own two-samples-per-lane kernel drm_forward_dynamics runs at this size (DRM_SPECIAL_FD_ARM2): from
         // DRM_ROLLOUT_COMPOSED_MIN_PAIRS pairs of tiles on, the composed steps are faster than the fused kernel
         if (w->special[DRM_SPECIAL_FD_ARM2] && w->special[DRM_SPECIAL_FD_ARM] && (B / WAVE) / 2 >= DRM_ROLLOUT_COMPOSED_MIN_PAIRS)
@@ -328,8 +328,7 @@ extern "C" int drm_forward_dynamics_rollout(const drm_walk *w, const float *q0, 
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
-    const bool aligned = ((((uintptr_t)q0 | (uintptr_t)qd0 | (uintptr_t)tau | (uintptr_t)q_traj | (uintptr_t)qd_traj |
-                            (uintptr_t)qdd_traj) & 15u) == 0);
+    const bool aligned = aligned16(q0, qd0, tau, q_traj, qd_traj, qdd_traj);
     const RolloutKind kind = rollout_kind(w, B, aligned);
     int64_t lo = 0;
     if (kind != ROLLOUT_COMPOSED) {
