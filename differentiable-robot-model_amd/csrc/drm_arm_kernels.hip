@@ -6,6 +6,7 @@
 #include "drm_common.hpp"
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
+#include "drm_arm_issue.hpp"
 
 namespace drm {
 
@@ -89,7 +90,8 @@ __global__ void __launch_bounds__(WAVE *WPB)
     // longest single item of a one-wave-per-SIMD launch) starts as early as possible: ang_jac needs only the joint
     // axes and goes out while the fixed tail of the chain is still being composed; lin_jac and pos need the end
     // position; the quaternion takes the most arithmetic and goes last.
-    fk_chain_pairs<CAP, NJ>([&](int k) -> const float * { if constexpr (PRE) return tabr[k]; else return lc + k * DRM_OPF_STRIDE; }, qv, ee, Bk, [&]() {
+    auto ft = [&](int k) -> const float * { if constexpr (PRE) return tabr[k]; else return lc + k * DRM_OPF_STRIDE; };
+    auto joints_done = [&]() {
         if constexpr (JAC) {
             float *arow = la + lane * SJ;
 #pragma unroll
@@ -100,7 +102,17 @@ __global__ void __launch_bounds__(WAVE *WPB)
             DRM_STAMP(2); // the moving joints are walked: first stores (ang_jac) go out
             tile_store<SJ, NT>(ang + b0 * SJ, WAVE, SJ, 0u, la, lane, true);
         }
-    });
+    };
+    if constexpr (PRE) {
+        // the lone wavefront of this form has nobody to fill the wait states between dependent packed operations: the four
+        // sincos evaluations advance in lock step and fill them with each other (drm_arm_issue.hpp; bit-identical results;
+        // 3.72 -> 3.65 us per launch on device events, profiles/metric_issue_slots.md).  The other forms keep chain_trig.
+        float cs[NJ], sn[NJ];
+        chain_trig_lockstep<NJ>(qv, cs, sn);
+        fk_chain_pairs_trig<CAP, NJ>(ft, cs, sn, ee, Bk, joints_done);
+    } else {
+        fk_chain_pairs<CAP, NJ>(ft, qv, ee, Bk, joints_done);
+    }
     DRM_STAMP(3); // chain done
 
     const float pe[3] = {ee.B[0][1], ee.B[1][1], ee.B[2][1]};
