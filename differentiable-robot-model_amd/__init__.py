@@ -11,6 +11,8 @@ from .robot_model import (  # noqa: F401
     DifferentiableFrankaPanda,
     DifferentiableTwoLinkRobot,
     DifferentiableTrifingerEdu,
+    InverseKinematicsResult,
+    OperationalSpaceDynamics,
 )
 
 __version__ = "0.1.0"

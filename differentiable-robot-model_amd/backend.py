@@ -26,6 +26,7 @@ ABI_VERSION = 15
 RNEA_GRAVITY, RNEA_DAMPING = 1, 2
 ROLLOUT_EXPLICIT_EULER = 4    # include/drm_hip.h DRM_ROLLOUT_EXPLICIT_EULER (ABI 14)
 IK_POSITION_ONLY, IK_COMPOSED = 1, 2     # include/drm_hip.h DRM_IK_POSITION_ONLY / DRM_IK_COMPOSED (ABI 15)
+OSC_POSITION_ONLY, OSC_COMPOSED = 8, 16  # include/drm_hip.h DRM_OSC_POSITION_ONLY / DRM_OSC_COMPOSED
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
 
@@ -85,7 +86,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned", "drm_special_load", "drm_fk_rnea_put",
            "drm_fk_mse_links", "drm_walk_table_links", "drm_walk_table_links_backward", "drm_forward_dynamics_rollout",
            "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned",
-           "drm_inverse_kinematics", "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned")
+           "drm_inverse_kinematics", "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned",
+           "drm_operational_space", "drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -183,6 +185,11 @@ def load_library(path: str = None, kind: str = "cuda"):
                      "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
+        lib.drm_operational_space.restype = ctypes.c_int
+        lib.drm_operational_space.argtypes = [wp, wp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]
+        for name in ("drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
         lib.drm_special_load.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.drm_fk_mse.restype = ctypes.c_int
@@ -932,6 +939,36 @@ def inverse_kinematics(prog: WalkProgram, ops_f, ops_i, q0, target_pos, target_q
                                           iters.data_ptr(), scratch.data_ptr() if scratch is not None else None,
                                           _stream(q0.device)), lib)
     return q, err, iters
+
+
+def operational_space(tree, chain, q, qd, include_gravity: bool, use_damping: bool, position_only: bool, reg: float, n_dofs: int,
+                      composed: bool = False):
+    """(inertia [B, m, m], jacobian_pinv [B, n, m], bias_acc [B, m], bias_force [B, m]), m = 3 if position_only else 6: the
+    operational-space dynamics of the target of the chain walk (include/drm_hip.h drm_operational_space).  ``tree`` and ``chain`` are
+    (program, ops_f, ops_i) of the dynamics walk and of the root -> link walk, as for fk_rnea.  ``composed`` forces the composed path
+    (DRM_OSC_COMPOSED: tests, A/B)."""
+    lib = _lib_of(q, "q", tree[1])
+    q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B:
+        raise ValueError("q / qd batch sizes differ")
+    m = 3 if position_only else 6
+    inertia, jbar, bias_acc, bias_force = _outputs(q.device, (B, m, m), (B, n_dofs, m), (B, m), (B, m))
+    if B == 0:
+        return inertia, jbar, bias_acc, bias_force
+    flags = ((RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) |
+             (OSC_POSITION_ONLY if position_only else 0) | (OSC_COMPOSED if composed else 0))
+    wt = _walk_struct(tree[0], tree[1].detach(), tree[2], n_dofs)
+    wc = _walk_struct(chain[0], chain[1].detach(), chain[2], n_dofs)
+    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_OSC_COMPOSED takes the composed path on every row: the size for any pointers)
+    query = lib.drm_operational_space_scratch_floats if composed else lib.drm_operational_space_scratch_floats_aligned
+    need = int(query(ctypes.byref(wt), ctypes.byref(wc), B))
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q.device):
+        _check(lib.drm_operational_space(ctypes.byref(wt), ctypes.byref(wc), q.data_ptr(), qd.data_ptr(), B, flags, float(reg),
+                                         inertia.data_ptr(), jbar.data_ptr(), bias_acc.data_ptr(), bias_force.data_ptr(),
+                                         scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    return inertia, jbar, bias_acc, bias_force
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

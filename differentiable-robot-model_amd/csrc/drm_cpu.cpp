@@ -22,6 +22,7 @@
 #include "drm_host_loops.hpp"
 #include "drm_link_forms.hpp"
 #include "drm_ik.hpp"
+#include "drm_osc.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -136,6 +137,56 @@ int rnea_checked(const drm_walk *w, const float *q, const float *qd, const float
     if (int rc = check_walk(w)) return rc;
     if (B < 0 || !q || !qd || !tau) return fail(DRM_ERR_INVALID, "bad batch or NULL q / qd / output");
     return DRM_OK;
+}
+
+// drm_operational_space, rows [b0, b0 + rows): jac_loop of the chain, crba_loop and rnea_loop (qdd = 0) of the tree, drm_osc.hpp
+template <int M>
+void osc_host_rows(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, int64_t b0, int64_t rows, int flags,
+                   float reg2, float *inertia, float *jbar, float *bias_acc, float *bias_force) {
+    const int n = tree->n_dofs;
+    const int32_t *w0 = chain->ops_i + DRM_OPI_W0 * chain->capacity;
+    std::vector<float> lin(3 * n), ang(3 * n), H((size_t)n * n), nle(n, 0.0f), Xv((size_t)M * n);
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd ? qd + b * n : nullptr;
+        bool ok = true;
+        for (int k = 0; k < n; ++k) ok = ok && std::isfinite(qr[k]) && (!qdr || std::isfinite(qdr[k]));
+        float Lam[M][M], acc[M] = {}, eta[M] = {};
+        auto J = [&](int r, int k) -> float { return r < 3 ? lin[r * n + k] : ang[(r - 3) * n + k]; };
+        auto X = [&](int r, int k) -> float & { return Xv[(size_t)r * n + k]; };
+        if (ok) {
+            jac_loop(chain, qr, 1, nullptr, nullptr, lin.data(), ang.data());
+            crba_loop(tree, qr, 1, H.data());
+            auto Hf = [&](int i, int j) -> float & { return H[(size_t)i * n + j]; };
+            drm::osc_ltdl_factor(n, Hf);
+            drm::osc_solve_columns<M>(n, Hf, J, X);
+            drm::osc_inertia<M>(n, J, X, reg2, Lam);
+            if (qdr) {
+                drm::osc_bias_acc<M>(chain->n_ops, [&](int k, float *z, float *r, bool &pris, float &v) {
+                    const int d = (w0[k] & 0xff) - 1;
+                    if (d < 0) return false;
+                    pris = (w0[k] >> 26) & 1;
+                    const float jp[3] = {lin[d], lin[n + d], lin[2 * n + d]};
+                    for (int i = 0; i < 3; ++i) z[i] = pris ? jp[i] : ang[i * n + d];
+                    drm::cross3(jp, z, r); // the point of the axis nearest to the target: r = (z x (p - p_k)) x z
+                    v = qdr[d];
+                    return true;
+                }, acc);
+                if (bias_force) {
+                    rnea_loop(tree, qr, qdr, nullptr, 1, flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING), nle.data());
+                    drm::osc_bias_force<M>(n, X, [&](int k) { return nle[k]; }, acc, Lam, eta);
+                }
+            }
+        }
+        for (int i = 0; i < M; ++i) {
+            for (int j = 0; j < M; ++j)
+                if (inertia) inertia[(b * M + i) * M + j] = ok ? Lam[i][j] : NAN;
+            if (bias_acc) bias_acc[b * M + i] = ok ? acc[i] : NAN;
+            if (bias_force) bias_force[b * M + i] = ok ? eta[i] : NAN;
+        }
+        if (jbar)
+            for (int k = 0; k < n; ++k)
+                for (int c = 0; c < M; ++c) jbar[(b * n + k) * M + c] = ok ? drm::osc_jbar<M>(X, Lam, k, c) : NAN;
+    }
 }
 } // namespace
 
@@ -318,6 +369,29 @@ int drm_inverse_kinematics(const drm_walk *w, const float *q0, const float *targ
                 }
             }
         }
+    });
+    return DRM_OK;
+}
+
+// Operational-space dynamics of one link: every row runs jac_loop of the chain, crba_loop and rnea_loop (qdd = 0) of the tree, then
+// drm_osc.hpp's arithmetic — the composed path of drm_osc.hip without its scratch
+int64_t drm_operational_space_scratch_floats(const drm_walk *, const drm_walk *, int64_t) { return 0; }
+int64_t drm_operational_space_scratch_floats_aligned(const drm_walk *, const drm_walk *, int64_t) { return 0; }
+
+int drm_operational_space(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, int64_t B, int32_t flags, float reg,
+                          float *inertia, float *jbar, float *bias_acc, float *bias_force, float *, void *) {
+    if (int rc = check_walk(tree)) return rc;
+    if (int rc = check_walk(chain)) return rc;
+    if (tree->n_dofs != chain->n_dofs) return fail(DRM_ERR_INVALID, "the two walks belong to different robots");
+    if (!inertia && !jbar && !bias_acc && !bias_force) return fail(DRM_ERR_INVALID, "every output is NULL");
+    if (!q || (!qd && (bias_acc || bias_force))) return fail(DRM_ERR_INVALID, "q must not be NULL, nor qd when bias_acc / bias_force are asked for");
+    if (!(reg >= 0.0f) || !std::isfinite(reg)) return fail(DRM_ERR_INVALID, "reg must be finite and >= 0");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    const bool pos_only = (flags & DRM_OSC_POSITION_ONLY) != 0;
+    const float *qd_used = bias_acc || bias_force ? qd : nullptr;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        if (pos_only) osc_host_rows<3>(tree, chain, q, qd_used, b0, rows, flags, reg * reg, inertia, jbar, bias_acc, bias_force);
+        else osc_host_rows<6>(tree, chain, q, qd_used, b0, rows, flags, reg * reg, inertia, jbar, bias_acc, bias_force);
     });
     return DRM_OK;
 }

@@ -18,7 +18,7 @@ live on a HIP device or if the native library is missing.
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -106,6 +106,15 @@ class InverseKinematicsResult:
     rot_err: Optional[torch.Tensor]     # [B] rotation angle between the target and the link's orientation at q; None: position only
     iterations: torch.Tensor            # [B] int32: the updates applied
     converged: torch.Tensor             # [B] bool: the errors are within the tolerances
+
+
+class OperationalSpaceDynamics(NamedTuple):
+    """What DifferentiableRobotModel.compute_operational_space_dynamics returns (no autograd history on any field); m = 6, or 3 in
+    position-only mode."""
+    inertia: torch.Tensor               # [B, m, m] (J H^-1 J^T + regularization^2 I)^-1
+    jacobian_pinv: torch.Tensor         # [B, n, m] H^-1 J^T inertia
+    bias_acc: torch.Tensor              # [B, m] Jdot qd
+    bias_force: torch.Tensor            # [B, m] inertia (J H^-1 nle - Jdot qd)
 
 
 class DifferentiableRobotModel(torch.nn.Module):
@@ -1540,6 +1549,66 @@ class DifferentiableRobotModel(torch.nn.Module):
             q, pos_err, iters, converged = q[0], pos_err[0], iters[0], converged[0]
             rot_err = rot_err[0] if rot_err is not None else None
         return InverseKinematicsResult(q=q, pos_err=pos_err, rot_err=rot_err, iterations=iters, converged=converged)
+
+    def compute_operational_space_dynamics(self, q: torch.Tensor, qd: torch.Tensor, link_name: str, *, include_gravity: bool = True,
+                                           use_damping: bool = False, position_only: bool = False, regularization: float = 0.0,
+                                           _composed: bool = False) -> OperationalSpaceDynamics:
+        """The operational-space (task-space) dynamics of ``link_name`` at q, qd [B, n]: what a task-space controller needs every
+        tick.  With H(q) qdd + nle(q, qd) = tau (nle = compute_non_linear_effects(q, qd, include_gravity, use_damping)),
+        J = [lin_jac; ang_jac] of compute_endeffector_jacobian(q, link_name) (m = 6 rows; lin_jac alone, m = 3, with
+        ``position_only``) and A = J H^-1 J^T + regularization^2 I:
+            inertia        [B, m, m]  A^-1, symmetric
+            jacobian_pinv  [B, n, m]  H^-1 J^T inertia, the dynamically consistent inverse of J
+            bias_acc       [B, m]     Jdot qd = d/dt J(q + t qd)|t=0 qd: the world-frame classical acceleration of the link origin
+                                      (rows 0-2) and its angular acceleration (rows 3-5) at qdd = 0, gravity absent
+            bias_force     [B, m]     inertia (J H^-1 nle - Jdot qd)
+        so that tau = J^T (inertia a + bias_force) produces the link acceleration a when regularization = 0.  One kernel launch for
+        a 7-DoF arm whose last link is the target (csrc/drm_osc.hip: one pass over q, no intermediate in HBM); the Jacobian, inertia
+        matrix and bias-torque kernels followed by a one-lane-per-row finish kernel for every other robot or link.  Unbatched q, qd
+        [n] give unbatched results.
+
+        At a SINGULAR configuration (J without full row rank: a stretched arm, or more task rows than the chain has joints) with
+        ``regularization=0`` A has no inverse: inertia — and with it jacobian_pinv and bias_force — is huge or non-finite on that
+        row only; no other row changes and nothing faults.  A positive ``regularization`` bounds |inertia| by 1 / regularization^2.
+        A row whose q or qd is not finite returns non-finite values and changes no other row.
+
+        The results carry NO autograd history, even when the inputs or the learnable link parameters require grad.  A model with
+        learnable links uses their current values.  (``_composed``: every row takes the composed path, DRM_OSC_COMPOSED; for tests
+        and A/B measurements.)"""
+        for name, t in (("q", q), ("qd", qd)):
+            if type(t) is not torch.Tensor:
+                raise TypeError("%s must be a tensor" % name)
+            if t.device.type != self._device.type:
+                raise ValueError("%s is on %s, the model on %s" % (name, t.device, self._device))
+            if not t.is_floating_point():
+                raise TypeError("%s must be a floating-point tensor (got %s)" % (name, t.dtype))
+        if q.ndim not in (1, 2) or q.shape[-1] != self._n_dofs:
+            raise ValueError("q must be [B, %d] or [%d], got %s" % (self._n_dofs, self._n_dofs, tuple(q.shape)))
+        if qd.shape != q.shape:
+            raise ValueError("qd must be %s like q, got %s" % (tuple(q.shape), tuple(qd.shape)))
+        if link_name not in self._name_to_idx_map:
+            raise ValueError("unknown link %r" % (link_name,))
+        idx = self._name_to_idx_map[link_name]
+        if idx == 0:
+            raise ValueError("%r is the root link: it does not move" % (link_name,))
+        regularization = float(regularization)
+        if not (math.isfinite(regularization) and regularization >= 0):
+            raise ValueError("regularization must be finite and >= 0 (got %r)" % (regularization,))
+        single = q.ndim == 1
+        if single:
+            q, qd = q.unsqueeze(0), qd.unsqueeze(0)
+        self._require_device()
+        with torch.no_grad():
+            tree = self._dynamics_walk()
+            chain = self._get_walk(("chain", idx) + (("folded", tree.fold_key) if tree.folded else ()), targets=[idx],
+                                   folded=tree.folded, fold_key=tree.fold_key)
+            out = backend.operational_space((tree.program, self._ops_f(tree).detach(), tree.ops_i),
+                                            (chain.program, self._ops_f(chain).detach(), chain.ops_i), q.detach(), qd.detach(),
+                                            bool(include_gravity), bool(use_damping), bool(position_only), regularization,
+                                            self._n_dofs, composed=bool(_composed))
+        if single:
+            out = tuple(t[0] for t in out)
+        return OperationalSpaceDynamics(*out)
 
     def compute_forward_dynamics_old(self, q: torch.Tensor, qd: torch.Tensor, f: torch.Tensor,
                                      include_gravity: Optional[bool] = True, use_damping: Optional[bool] = True

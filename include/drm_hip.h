@@ -199,6 +199,9 @@ extern "C" {
 /* flags of drm_inverse_kinematics (ABI 15) */
 #define DRM_IK_POSITION_ONLY 1 /* target_pos only: a 3 x 3 system, rot_err written as 0 */
 #define DRM_IK_COMPOSED 2      /* force the composed path on every row (tests, A/B) */
+/* flags of drm_operational_space, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
+#define DRM_OSC_POSITION_ONLY 8 /* J = lin_jac alone: a 3 x 3 task space */
+#define DRM_OSC_COMPOSED 16     /* force the composed path on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -458,6 +461,37 @@ int64_t drm_inverse_kinematics_scratch_floats_aligned(const drm_walk *walk, int6
 int drm_inverse_kinematics(const drm_walk *walk, const float *q0, const float *target_pos, const float *target_quat, int64_t B,
                            int32_t max_iters, float damping, float step, float tol_pos, float tol_rot, const float *lower,
                            const float *upper, int32_t flags, float *q, float *err, int32_t *iters, float *scratch, void *stream);
+
+/*
+ * Operational-space dynamics of one link in one call (additive to ABI 15): what a task-space controller needs every tick, and
+ * what a caller otherwise composes from drm_fk_jacobian, drm_crba, drm_rnea with qdd = NULL and a chain of small dense solves.
+ * With H(q) qdd + nle(q, qd) = tau (nle as drm_rnea with qdd = NULL and the same gravity / damping flags), J = [lin_jac; ang_jac]
+ * of drm_fk_jacobian (m = 6 rows; m = 3, lin_jac alone, with DRM_OSC_POSITION_ONLY) and A = J H^-1 J^T + reg^2 I (m x m):
+ *   inertia    [B, m, m]  A^-1, the task-space inertia (symmetric)
+ *   jbar       [B, n, m]  H^-1 J^T inertia, the dynamically consistent inverse of J
+ *   bias_acc   [B, m]     Jdot qd: the world-frame classical acceleration of the link origin (rows 0-2) and the angular
+ *                         acceleration of the link (rows 3-5) at zero joint accelerations, gravity absent
+ *   bias_force [B, m]     inertia (J H^-1 nle - Jdot qd)
+ * so that tau = J^T (inertia a + bias_force) produces the link acceleration a when reg = 0.
+ *   tree, chain  as for drm_fk_rnea: the whole-tree walk and the root->link walk, folded trees allowed in the same way
+ *   q, qd [B, n];  flags: DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING | DRM_OSC_POSITION_ONLY | DRM_OSC_COMPOSED;  reg >= 0
+ *   Any of the four outputs may be NULL: that array is not written.  qd may be NULL when neither bias_acc nor bias_force is asked for.
+ * A serial 7-DoF arm whose target is the chain's last link (where drm_fk_rnea fuses), full 64-row tiles, 16-byte aligned pointers:
+ * ONE kernel, one wavefront per tile — one sin / cos evaluation shared by the bias torques, H and the Jacobian, H factorised once
+ * (L^T D L) in registers and solved against the m rows of J, A inverted by Cholesky, no intermediate in HBM (56 B in per row).
+ * Every other robot, a mid-chain target, the ragged tail, misaligned pointers and DRM_OSC_COMPOSED: drm_fk_jacobian, drm_crba and
+ * drm_rnea into the scratch, then a finish kernel with one lane per row.  A row whose q or qd is not finite gets non-finite
+ * outputs and changes no other row; a singular configuration with reg = 0 gives a huge or non-finite inertia on that row only.
+ *   scratch   drm_operational_space_scratch_floats_aligned floats when every pointer (scratch included) is 16-byte aligned (0 when
+ *             the fused kernel covers every row; scratch may then be NULL), drm_operational_space_scratch_floats floats otherwise
+ *             and with DRM_OSC_COMPOSED
+ * DRM_ERR_INVALID when reg is negative or not finite, a required pointer is NULL or every output is NULL; B == 0 returns DRM_OK.
+ * Asynchronous on `stream`, never a host synchronisation.
+ */
+int64_t drm_operational_space_scratch_floats(const drm_walk *tree, const drm_walk *chain, int64_t B);
+int64_t drm_operational_space_scratch_floats_aligned(const drm_walk *tree, const drm_walk *chain, int64_t B);
+int drm_operational_space(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, int64_t B, int32_t flags,
+                          float reg, float *inertia, float *jbar, float *bias_acc, float *bias_force, float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
