@@ -13,6 +13,7 @@ from .robot_model import (  # noqa: F401
     DifferentiableTrifingerEdu,
     InverseKinematicsResult,
     OperationalSpaceDynamics,
+    ForwardDynamicsDerivatives,
 )
 
 __version__ = "0.1.0"

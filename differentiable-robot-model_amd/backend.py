@@ -27,6 +27,7 @@ RNEA_GRAVITY, RNEA_DAMPING = 1, 2
 ROLLOUT_EXPLICIT_EULER = 4    # include/drm_hip.h DRM_ROLLOUT_EXPLICIT_EULER (ABI 14)
 IK_POSITION_ONLY, IK_COMPOSED = 1, 2     # include/drm_hip.h DRM_IK_POSITION_ONLY / DRM_IK_COMPOSED (ABI 15)
 OSC_POSITION_ONLY, OSC_COMPOSED = 8, 16  # include/drm_hip.h DRM_OSC_POSITION_ONLY / DRM_OSC_COMPOSED
+FDD_COMPOSED = 32             # include/drm_hip.h DRM_FDD_COMPOSED
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
 
@@ -87,7 +88,9 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_fk_mse_links", "drm_walk_table_links", "drm_walk_table_links_backward", "drm_forward_dynamics_rollout",
            "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned",
            "drm_inverse_kinematics", "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned",
-           "drm_operational_space", "drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned")
+           "drm_operational_space", "drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned",
+           "drm_forward_dynamics_derivatives", "drm_forward_dynamics_derivatives_scratch_floats",
+           "drm_forward_dynamics_derivatives_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -190,6 +193,11 @@ def load_library(path: str = None, kind: str = "cuda"):
         for name in ("drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, wp, i64]
+        lib.drm_forward_dynamics_derivatives.restype = ctypes.c_int
+        lib.drm_forward_dynamics_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
+        for name in ("drm_forward_dynamics_derivatives_scratch_floats", "drm_forward_dynamics_derivatives_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
         lib.drm_special_load.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.drm_fk_mse.restype = ctypes.c_int
@@ -969,6 +977,35 @@ def operational_space(tree, chain, q, qd, include_gravity: bool, use_damping: bo
                                          inertia.data_ptr(), jbar.data_ptr(), bias_acc.data_ptr(), bias_force.data_ptr(),
                                          scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return inertia, jbar, bias_acc, bias_force
+
+
+def forward_dynamics_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, f, include_gravity: bool, use_damping: bool, n_dofs: int,
+                                 composed: bool = False):
+    """(qdd [B, n], dqdd_dq [B, n, n], dqdd_dqd [B, n, n], minv [B, n, n]): forward dynamics and its linearisation about (q, qd, f)
+    (include/drm_hip.h drm_forward_dynamics_derivatives).  ``composed`` (or DRM_FDD_COMPOSED=1 in the environment) forces the
+    composed path (DRM_FDD_COMPOSED: tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    if not prog.slots_unique:
+        raise RuntimeError("backward RNEA needs a walk whose branch points own their save slots")
+    q, qd, f = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(f, "f", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B or f.shape[0] != B:
+        raise ValueError("q / qd / f batch sizes differ")
+    qdd, dq, dqd, minv = _outputs(q.device, (B, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs))
+    if B == 0:
+        return qdd, dq, dqd, minv
+    composed = bool(composed) or os.environ.get("DRM_FDD_COMPOSED") == "1"
+    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (FDD_COMPOSED if composed else 0)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_FDD_COMPOSED takes the composed path on every row: the size for any pointers)
+    query = lib.drm_forward_dynamics_derivatives_scratch_floats if composed else lib.drm_forward_dynamics_derivatives_scratch_floats_aligned
+    need = int(query(ctypes.byref(walk), B))
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q.device):
+        _check(lib.drm_forward_dynamics_derivatives(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), f.data_ptr(), B, flags,
+                                                    qdd.data_ptr(), dq.data_ptr(), dqd.data_ptr(), minv.data_ptr(),
+                                                    scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    return qdd, dq, dqd, minv
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

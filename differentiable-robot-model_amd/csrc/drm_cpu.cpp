@@ -23,6 +23,7 @@
 #include "drm_link_forms.hpp"
 #include "drm_ik.hpp"
 #include "drm_osc.hpp"
+#include "drm_fdd.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -186,6 +187,37 @@ void osc_host_rows(const drm_walk *tree, const drm_walk *chain, const float *q, 
         if (jbar)
             for (int k = 0; k < n; ++k)
                 for (int c = 0; c < M; ++c) jbar[(b * n + k) * M + c] = ok ? drm::osc_jbar<M>(X, Lam, k, c) : NAN;
+    }
+}
+// drm_forward_dynamics_derivatives, rows [b0, b0 + rows): fd_loop and crba_loop of the row, one reverse sweep of RNEA (rneab_t) per
+// row of dID/dq and dID/dqd, then drm_fdd.hpp's inverse and solves
+void fdd_host_rows(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t b0, int64_t rows, int flags, float *qdd,
+                   float *dq, float *dqd, float *minv) {
+    const int n = w->n_dofs;
+    std::vector<float> H((size_t)n * n), work(n), acc(n), seed(n), gqdd(n);
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd + b * n, *fr = f + b * n;
+        bool ok = true;
+        for (int k = 0; k < n; ++k) ok = ok && std::isfinite(qr[k]) && std::isfinite(qdr[k]) && std::isfinite(fr[k]);
+        float *Dq = dq + b * n * n, *Dqd = dqd + b * n * n, *Mo = minv + b * n * n;
+        if (!ok) {
+            for (int k = 0; k < n; ++k) qdd[b * n + k] = NAN;
+            for (int k = 0; k < n * n; ++k) Dq[k] = Dqd[k] = Mo[k] = NAN;
+            continue;
+        }
+        fd_loop(w, qr, qdr, fr, 1, flags, acc.data());
+        crba_loop(w, qr, 1, H.data());
+        for (int k = 0; k < n; ++k) { // row k of dID/dq and dID/dqd, in place in the outputs
+            for (int d = 0; d < n; ++d) seed[d] = d == k ? 1.0f : 0.0f;
+            rneab_t(w, qr, qdr, acc.data(), 1, flags, seed.data(), 0, Dq + k * n, Dqd + k * n, gqdd.data(), nullptr);
+        }
+        auto Hf = [&](int i, int j) -> float & { return H[(size_t)i * n + j]; };
+        auto wf = [&](int i) -> float & { return work[i]; };
+        drm::fdd_ltdl_factor<float>(n, Hf);
+        drm::fdd_inverse<float>(n, Hf, wf, [&](int i, int c, float v) { Mo[i * n + c] = v; Mo[c * n + i] = v; });
+        drm::fdd_solve_columns<float>(n, Hf, wf, [&](int i, int j) { return Dq[i * n + j]; }, [&](int i, int j, float v) { Dq[i * n + j] = v; });
+        drm::fdd_solve_columns<float>(n, Hf, wf, [&](int i, int j) { return Dqd[i * n + j]; }, [&](int i, int j, float v) { Dqd[i * n + j] = v; });
+        for (int k = 0; k < n; ++k) qdd[b * n + k] = acc[k];
     }
 }
 } // namespace
@@ -393,6 +425,22 @@ int drm_operational_space(const drm_walk *tree, const drm_walk *chain, const flo
         if (pos_only) osc_host_rows<3>(tree, chain, q, qd_used, b0, rows, flags, reg * reg, inertia, jbar, bias_acc, bias_force);
         else osc_host_rows<6>(tree, chain, q, qd_used, b0, rows, flags, reg * reg, inertia, jbar, bias_acc, bias_force);
     });
+    return DRM_OK;
+}
+
+// Forward-dynamics derivatives: every row runs fd_loop, crba_loop, n reverse sweeps of RNEA and drm_fdd.hpp's inverse and solves — the
+// composed path of drm_fdd.hip without its scratch.  The walks drm_rnea_backward refuses are refused here, with its message.
+int64_t drm_forward_dynamics_derivatives_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_forward_dynamics_derivatives_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_forward_dynamics_derivatives(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int32_t flags,
+                                     float *qdd, float *dq, float *dqd, float *minv, float *, void *) {
+    if (int rc = check_backward_walk(w, 0)) return rc;
+    if (!q || !qd || !f) return fail(DRM_ERR_INVALID, "q / qd / f must not be NULL");
+    if (!qdd || !dq || !dqd || !minv) return fail(DRM_ERR_INVALID, "qdd / dqdd_dq / dqdd_dqd / minv must not be NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    const int fl = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { fdd_host_rows(w, q, qd, f, b0, rows, fl, qdd, dq, dqd, minv); });
     return DRM_OK;
 }
 

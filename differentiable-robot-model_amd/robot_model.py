@@ -117,6 +117,14 @@ class OperationalSpaceDynamics(NamedTuple):
     bias_force: torch.Tensor            # [B, m] inertia (J H^-1 nle - Jdot qd)
 
 
+class ForwardDynamicsDerivatives(NamedTuple):
+    """What DifferentiableRobotModel.compute_forward_dynamics_derivatives returns (no autograd history on any field)."""
+    qdd: torch.Tensor                   # [B, n] = compute_forward_dynamics(q, qd, f, ...)
+    dqdd_dq: torch.Tensor               # [B, n, n] [b, i, j] = d qdd_i / d q_j
+    dqdd_dqd: torch.Tensor              # [B, n, n] [b, i, j] = d qdd_i / d qd_j (with use_damping it includes -H^-1 diag(damping))
+    minv: torch.Tensor                  # [B, n, n] H(q)^-1 = d qdd / d f, symmetric
+
+
 class DifferentiableRobotModel(torch.nn.Module):
     """Batched FK / geometric Jacobian / RNEA on MI355X behind the reference API."""
 
@@ -1609,6 +1617,45 @@ class DifferentiableRobotModel(torch.nn.Module):
         if single:
             out = tuple(t[0] for t in out)
         return OperationalSpaceDynamics(*out)
+
+    def compute_forward_dynamics_derivatives(self, q: torch.Tensor, qd: torch.Tensor, f: torch.Tensor,
+                                             include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False, *,
+                                             _composed: bool = False) -> ForwardDynamicsDerivatives:
+        """Forward dynamics and its linearisation about the state (q, qd) and the torques f [B, n]: what iLQR / DDP, LQR, linearised
+        MPC and an EKF need at every knot.  With ID(q, qd, qdd) = H(q) qdd + nle(q, qd) the inverse dynamics (the damping torques
+        inside when ``use_damping``):
+            qdd       [B, n]     compute_forward_dynamics(q, qd, f, include_gravity, use_damping)
+            dqdd_dq   [B, n, n]  [b, i, j] = d qdd_i / d q_j  = -(H^-1 dID/dq)[i, j] at (q, qd, qdd)
+            dqdd_dqd  [B, n, n]  [b, i, j] = d qdd_i / d qd_j = -(H^-1 dID/dqd)[i, j]
+            minv      [B, n, n]  H(q)^-1 = d qdd / d f, symmetric
+        so that A = [dqdd_dq, dqdd_dqd] and B = minv linearise the continuous dynamics.  One kernel launch for a 7-DoF arm
+        (csrc/drm_fdd.hip: one pass over q, one factorisation of H, n reverse sweeps of RNEA for the rows of dID/dq and dID/dqd, 3 n
+        solves, no intermediate in HBM; qdd from the forward-dynamics kernel itself when the robot's own kernels are attached); for every
+        other robot the forward-dynamics and inertia-matrix kernels, n launches of the RNEA
+        backward kernel and a one-lane-per-row kernel that inverts and solves, all out of one scratch allocation.  Argument handling is that of
+        compute_forward_dynamics (unbatched inputs give unbatched results); ``f`` is never modified.  A row whose q, qd or f is not
+        finite returns non-finite values and changes no other row.  Robots whose trees the backward kernels do not take (more than
+        64 links or 6 open branch points) are refused as a gradient of compute_forward_dynamics would be.
+
+        The results carry NO autograd history, even when the inputs or the learnable link parameters require grad.  A model with
+        learnable links uses their current values.  (``_composed``, or DRM_FDD_COMPOSED=1 in the environment: every row takes the
+        composed path, DRM_FDD_COMPOSED; for tests and A/B measurements.)"""
+        return ForwardDynamicsDerivatives(*self._compute_forward_dynamics_derivatives(q, qd, f, include_gravity, use_damping,
+                                                                                      bool(_composed)))
+
+    @tensor_check
+    def _compute_forward_dynamics_derivatives(self, q, qd, f, include_gravity, use_damping, composed):
+        assert q.ndim == 2
+        assert qd.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        assert qd.shape[1] == self._n_dofs
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            self._differentiable(dw)
+            return backend.forward_dynamics_derivatives(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(),
+                                                        f.detach(), bool(include_gravity), bool(use_damping), self._n_dofs,
+                                                        composed=composed)
 
     def compute_forward_dynamics_old(self, q: torch.Tensor, qd: torch.Tensor, f: torch.Tensor,
                                      include_gravity: Optional[bool] = True, use_damping: Optional[bool] = True

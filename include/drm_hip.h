@@ -202,6 +202,8 @@ extern "C" {
 /* flags of drm_operational_space, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
 #define DRM_OSC_POSITION_ONLY 8 /* J = lin_jac alone: a 3 x 3 task space */
 #define DRM_OSC_COMPOSED 16     /* force the composed path on every row (tests, A/B) */
+/* flag of drm_forward_dynamics_derivatives, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
+#define DRM_FDD_COMPOSED 32     /* force the composed path on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -492,6 +494,35 @@ int64_t drm_operational_space_scratch_floats(const drm_walk *tree, const drm_wal
 int64_t drm_operational_space_scratch_floats_aligned(const drm_walk *tree, const drm_walk *chain, int64_t B);
 int drm_operational_space(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, int64_t B, int32_t flags,
                           float reg, float *inertia, float *jbar, float *bias_acc, float *bias_force, float *scratch, void *stream);
+
+/*
+ * The linearisation of forward dynamics about a state in one call (additive to ABI 15): what iLQR / DDP, LQR, linearised MPC and an
+ * EKF need at every knot, and what a caller otherwise gets from n backward passes through drm_forward_dynamics with one-hot
+ * cotangents.  With ID(q, qd, qdd) = H(q) qdd + nle(q, qd) (drm_rnea with the same gravity / damping flags) and qdd = H^-1 (f - nle):
+ *   qdd   [B, n]      what drm_forward_dynamics computes from the same inputs
+ *   dq    [B, n, n]   [b, i, j] = d qdd_i / d q_j  = -(H^-1 dID/dq)[i, j] at (q, qd, qdd)
+ *   dqd   [B, n, n]   [b, i, j] = d qdd_i / d qd_j = -(H^-1 dID/dqd)[i, j]; with DRM_RNEA_DAMPING it includes -H^-1 diag(damping)
+ *   minv  [B, n, n]   H(q)^-1 = d qdd / d f, symmetric to the bit
+ *   q, qd, f [B, n] (f is not modified);  flags: DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING | DRM_FDD_COMPOSED.  No output may be NULL.
+ * Row k of dID/dq and dID/dqd is the reverse sweep of RNEA seeded with grad_tau = e_k; the outputs are 3 n solves with ONE L^T D L
+ * factorisation of H.  Serial 7-DoF arm chains, full 64-row tiles, 16-byte aligned pointers (what drm_forward_dynamics' arm kernel
+ * takes): ONE kernel, one wavefront per tile, one row per lane — one sin / cos evaluation, H by the composite walk factorised once
+ * in registers, qdd, H^-1, then the n sweeps and the 2 n solves; the three matrices leave through LDS in 16-byte stores (84 B in,
+ * 616 B out per row, nothing else through HBM).  A walk that carries its robot's own forward-dynamics kernel (special[DRM_SPECIAL_FD*])
+ * gets qdd from drm_forward_dynamics in a second launch: the same values as that call, to the bit.  Every other robot, the ragged tail, misaligned pointers and DRM_FDD_COMPOSED:
+ * drm_forward_dynamics, drm_crba and n calls of drm_rnea_backward (grad_tau = e_k) into the scratch, then a finish kernel with one
+ * lane per row that factorises H, inverts and solves (n <= 16: in registers; else in LDS, or in the scratch where 64 rows do not
+ * fit).  A row whose q, qd or f is not finite gets non-finite outputs and changes no other row.
+ *   scratch   drm_forward_dynamics_derivatives_scratch_floats_aligned floats when every pointer (scratch included) is 16-byte
+ *             aligned (0 when the fused kernel covers every row; scratch may then be NULL),
+ *             drm_forward_dynamics_derivatives_scratch_floats floats otherwise and with DRM_FDD_COMPOSED
+ * DRM_ERR_UNSUPPORTED for a walk the backward kernels do not take (more than DRM_MAX_OPS ops or DRM_MAX_SLOTS_BACKWARD save slots);
+ * DRM_ERR_INVALID when a pointer is NULL; B == 0 returns DRM_OK.  Asynchronous on `stream`, never a host synchronisation.
+ */
+int64_t drm_forward_dynamics_derivatives_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_forward_dynamics_derivatives_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_forward_dynamics_derivatives(const drm_walk *walk, const float *q, const float *qd, const float *f, int64_t B, int32_t flags,
+                                     float *qdd, float *dq, float *dqd, float *minv, float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
