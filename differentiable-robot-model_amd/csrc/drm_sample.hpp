@@ -35,8 +35,25 @@
 // true if the predicate holds in any lane of the wavefront (the host emulation runs one sample at a time)
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DRM_WAVE_ANY(pred) (__builtin_amdgcn_ballot_w64(pred) != 0ull)
+// The same for a rare escape whose body selects per lane on the same predicate: the mask passes through an empty asm, so that the
+// compiler cannot fold `if (any(p)) { if (p) ... }` into a divergent `if (p)` and the test stays ONE scalar branch on the common path.
+static __device__ __forceinline__ bool drm_wave_any_rare(bool pred) {
+    unsigned long long mask = __builtin_amdgcn_ballot_w64(pred);
+    asm volatile("" : "+s"(mask));
+    return __builtin_expect(mask != 0ull, 0);
+}
+#define DRM_WAVE_ANY_RARE(pred) drm_wave_any_rare(pred)
+// a value as the rare block sees it: opaque too, so that the block's copy of the common evaluation is not merged with (hoisted above
+// the branch of) the common path's, which would put the per-lane selection's execution masks on the common path
+static __device__ __forceinline__ float drm_rare_copy(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+#define DRM_RARE_COPY(x) drm_rare_copy(x)
 #else
 #define DRM_WAVE_ANY(pred) (pred)
+#define DRM_WAVE_ANY_RARE(pred) (pred)
+#define DRM_RARE_COPY(x) (x)
 #endif
 
 namespace drm {
@@ -384,12 +401,8 @@ constexpr float SINCOS_PAIR_MAX_ARG = 1.0e5f;
 //                     (the kernel starts storing the angular Jacobian while the fixed tail is still computed)
 // Out: B[k][c] = (z_c, p_c) of every moving joint k, and the end pose.
 // sin / cos of one joint angle: sincos_pair's algorithm on scalars (same constants, same operation order), with the
-// same wave-uniform escape to the fp64 reduction for |x| > 1e5
-DRM_HD void sincos_one(float x, float &s, float &c) {
-    if (DRM_WAVE_ANY(!(fabsf(x) <= SINCOS_PAIR_MAX_ARG))) {
-        sincos_f(x, s, c);
-        return;
-    }
+// same escape to the fp64 reduction for |x| > 1e5 or a non-finite x
+DRM_HD void sincos_one_packed(float x, float &s, float &c) {
     const float magic = 12582912.0f;
     const float kb = __builtin_fmaf(x, 0.318309886f, magic);
     const float kf = kb - magic;
@@ -412,24 +425,48 @@ DRM_HD void sincos_one(float x, float &s, float &c) {
     s = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, sr) ^ flip);
     c = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, cr) ^ flip);
 }
+// The escape is entered by the whole wavefront (one scalar branch on the common path) when any lane holds such an angle, but only
+// those lanes take sincos_f's values: the others keep the packed evaluation's, bit for bit, so that a row never depends on the rows
+// it shares a wavefront with.
+DRM_HD void sincos_one(float x, float &s, float &c) {
+    const bool big = !(fabsf(x) <= SINCOS_PAIR_MAX_ARG);
+    if (DRM_WAVE_ANY_RARE(big)) {
+        const float xr = DRM_RARE_COPY(x);
+        if (big) sincos_f(xr, s, c);
+        else sincos_one_packed(xr, s, c);
+        return;
+    }
+    sincos_one_packed(x, s, c);
+}
 
 // cos / sin of the NJ joint angles of a chain, two joints per packed evaluation
+template <int NJ>
+DRM_HD void chain_trig_packed(const float (&q)[NJ], float (&cs)[NJ], float (&sn)[NJ]) {
+#pragma unroll
+    for (int d = 0; d < NJ; d += 2) {
+        f2 s2, c2;
+        sincos_pair(f2_make(q[d], q[d + 1 < NJ ? d + 1 : d]), s2, c2);
+        sn[d] = s2[0]; cs[d] = c2[0];
+        if (d + 1 < NJ) { sn[d + 1] = s2[1]; cs[d + 1] = c2[1]; }
+    }
+}
 template <int NJ>
 DRM_HD void chain_trig(const float (&q)[NJ], float (&cs)[NJ], float (&sn)[NJ]) {
     bool big = false;
 #pragma unroll
     for (int d = 0; d < NJ; ++d) big = big || !(fabsf(q[d]) <= SINCOS_PAIR_MAX_ARG);
-    if (DRM_WAVE_ANY(big)) { // rare; wave-uniform, so the common path carries no execution-mask juggling
+    if (DRM_WAVE_ANY_RARE(big)) { // wave-uniform, so the common path carries no execution-mask juggling; lane by lane inside (sincos_one)
+        float qr[NJ];
 #pragma unroll
-        for (int d = 0; d < NJ; ++d) sincos_f(q[d], sn[d], cs[d]);
-    } else {
+        for (int d = 0; d < NJ; ++d) qr[d] = DRM_RARE_COPY(q[d]);
+        if (big) {
 #pragma unroll
-        for (int d = 0; d < NJ; d += 2) {
-            f2 s2, c2;
-            sincos_pair(f2_make(q[d], q[d + 1 < NJ ? d + 1 : d]), s2, c2);
-            sn[d] = s2[0]; cs[d] = c2[0];
-            if (d + 1 < NJ) { sn[d + 1] = s2[1]; cs[d + 1] = c2[1]; }
+            for (int d = 0; d < NJ; ++d) sincos_f(qr[d], sn[d], cs[d]);
+        } else {
+            chain_trig_packed<NJ>(qr, cs, sn);
         }
+    } else {
+        chain_trig_packed<NJ>(q, cs, sn);
     }
 }
 // the chain itself, given cos / sin of the joint angles (the fused FK + RNEA kernel shares them between its two walks)
@@ -1357,16 +1394,30 @@ DRM_HD void fk_chain2_trig(ROW row, const f2 (&cs)[NJ], const f2 (&sn)[NJ], Pose
 // cos / sin of the NJ joint angles of two samples
 template <int NJ>
 DRM_HD void chain_trig2(const f2 (&q)[NJ], f2 (&cs)[NJ], f2 (&sn)[NJ]) {
-    bool big = false;
+    bool big0 = false, big1 = false;
 #pragma unroll
-    for (int d = 0; d < NJ; ++d) big = big || !(fabsf(q[d][0]) <= SINCOS_PAIR_MAX_ARG) || !(fabsf(q[d][1]) <= SINCOS_PAIR_MAX_ARG);
-    if (DRM_WAVE_ANY(big)) { // rare; wave-uniform
+    for (int d = 0; d < NJ; ++d) {
+        big0 = big0 || !(fabsf(q[d][0]) <= SINCOS_PAIR_MAX_ARG);
+        big1 = big1 || !(fabsf(q[d][1]) <= SINCOS_PAIR_MAX_ARG);
+    }
+    if (DRM_WAVE_ANY_RARE(big0 || big1)) { // wave-uniform; sample by sample inside (chain_trig)
+        f2 qr[NJ];
 #pragma unroll
-        for (int d = 0; d < NJ; ++d) {
-            float s0, c0, s1, c1;
-            sincos_f(q[d][0], s0, c0);
-            sincos_f(q[d][1], s1, c1);
-            sn[d] = f2_make(s0, s1); cs[d] = f2_make(c0, c1);
+        for (int d = 0; d < NJ; ++d) qr[d] = f2_make(DRM_RARE_COPY(q[d][0]), DRM_RARE_COPY(q[d][1]));
+        if (big0 || big1) {
+#pragma unroll
+            for (int d = 0; d < NJ; ++d) {
+                // (a lane whose other sample is in range: that sample's packed values, element-wise the same as the pair's)
+                f2 sp, cp;
+                sincos_pair(qr[d], sp, cp);
+                float s0 = sp[0], c0 = cp[0], s1 = sp[1], c1 = cp[1];
+                if (big0) sincos_f(qr[d][0], s0, c0);
+                if (big1) sincos_f(qr[d][1], s1, c1);
+                sn[d] = f2_make(s0, s1); cs[d] = f2_make(c0, c1);
+            }
+        } else {
+#pragma unroll
+            for (int d = 0; d < NJ; ++d) sincos_pair(qr[d], sn[d], cs[d]);
         }
     } else {
 #pragma unroll

@@ -2,7 +2,8 @@
 """Generate tests/golden/golden_rollout.npz: rollouts of the UNMODIFIED reference (its `compute_forward_dynamics`,
 robot_model.py:487-624, called in a Python loop with the Euler integrators of compute_forward_dynamics_rollout) and the
 reference autograd's gradients of a fixed scalar loss on the trajectory with respect to q0, qd0, tau and one learnable link
-mass (PositiveScalar, rigid_body_params.py:26-43, started at 1.2 times the URDF's mass).
+mass (PositiveScalar, rigid_body_params.py:26-43, started at 1.2 times the URDF's mass), for both rollouts of RUNS: under
+"<robot>/grad/..." for the first (semi-implicit Euler, gravity) and "<robot>/grad_<key>/..." for every further one.
 
 Every step passes a CLONE of tau[t]: the reference subtracts the damping torques from its `f` argument in place.
 
@@ -81,18 +82,21 @@ def main():
         learn.make_link_param_learnable(link, "mass", rbp.PositiveScalar(init_param=torch.tensor(1.2 * mass)))
         mod = learn._bodies[learn._name_to_idx_map[link]].inertia.mass
         mk = lambda a: torch.tensor(a, requires_grad=True)
-        q0t, qd0t, taut = mk(q0), mk(qd0), mk(tau)
-        qt, qdt = rollout(learn, q0t, qd0t, taut, "semi_implicit_euler", True, False)
-        loss = loss_of(qt, qdt)
-        assert torch.isfinite(loss), name
-        loss.backward()
         out[name + "/grad/link"] = np.asarray(link)
         out[name + "/grad/l"] = mod.l.detach().numpy().copy()
-        out[name + "/grad/loss"] = np.asarray(loss.item(), np.float64)
-        out[name + "/grad/q0"], out[name + "/grad/qd0"], out[name + "/grad/tau"] = q0t.grad.numpy(), qd0t.grad.numpy(), taut.grad.numpy()
-        out[name + "/grad/l_grad"] = mod.l.grad.numpy().copy()
-        print("%-22s n=%2d |q_T - q0| max %.3g  loss %.5f  dL/dl %.4g" % (name, n, np.abs(qt[-1].detach().numpy() - q0).max(), loss.item(),
-                                                                       float(mod.l.grad)))
+        for i, (key, integ, grav, damp) in enumerate(RUNS):
+            pre = name + ("/grad/" if i == 0 else "/grad_%s/" % key)
+            q0t, qd0t, taut = mk(q0), mk(qd0), mk(tau)
+            mod.l.grad = None
+            qt, qdt = rollout(learn, q0t, qd0t, taut, integ, grav, damp)
+            loss = loss_of(qt, qdt)
+            assert torch.isfinite(loss), (name, key)
+            loss.backward()
+            out[pre + "loss"] = np.asarray(loss.item(), np.float64)
+            out[pre + "q0"], out[pre + "qd0"], out[pre + "tau"] = q0t.grad.numpy(), qd0t.grad.numpy(), taut.grad.numpy()
+            out[pre + "l_grad"] = mod.l.grad.numpy().copy()
+            print("%-22s %-11s n=%2d |q_T - q0| max %.3g  loss %.5f  dL/dl %.4g" % (name, key, n, np.abs(qt[-1].detach().numpy() - q0).max(),
+                                                                                 loss.item(), float(mod.l.grad)))
     np.savez_compressed(os.path.join(HERE, "golden_rollout.npz"), **out)
 
 

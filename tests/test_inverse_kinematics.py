@@ -9,6 +9,8 @@ misaligned launches, a full-size Panda solve and graph capture.
 The calibration setup (``seeded_problem``): q* uniform in the middle 80 % of each joint's range, target = FK(q*),
 q0 = clamp(q* + 0.1 N(0, 1)), damping 0.01, 32 iterations.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -390,7 +392,6 @@ def test_abi_entry_points():
     m = load("panda_no_gripper")
     dw = m._chain_walk(m._name_to_idx_map["panda_virtual_ee_link"])
     walk = backend._walk_struct(dw.program, m._ops_f(dw), dw.ops_i, 7)
-    import ctypes
     assert lib.drm_inverse_kinematics_scratch_floats(ctypes.byref(walk), 100) == 0
     q = torch.zeros(1, 7)
     out = torch.empty(1, 7)
@@ -474,10 +475,42 @@ def test_gpu_ragged_and_misaligned(robot, link):
     head = gpu.compute_inverse_kinematics(q0[:4096], link, tp[:4096], tq[:4096])
     tail = gpu.compute_inverse_kinematics(q0[4096:].clone(), link, tp[4096:].clone(), tq[4096:].clone())
     assert torch.equal(full.q, torch.cat([head.q, tail.q])) and torch.equal(full.iterations, torch.cat([head.iterations, tail.iterations]))
-    # an offset view (rows 1 ..): not 16-byte aligned
+    # an offset view (rows 1 ..), which the binding copies to an aligned tensor before the kernels see it
     view = gpu.compute_inverse_kinematics(q0[1:65], link, tp[1:65], tq[1:65])
     alone = gpu.compute_inverse_kinematics(q0[1:65].clone(), link, tp[1:65].clone(), tq[1:65].clone())
     assert torch.equal(view.q, alone.q) and torch.equal(view.iterations, alone.iterations)
+    # truly misaligned: q0, the targets and the outputs one float (or int) into larger buffers, straight through the C ABI: ik_fused(..., aligned = false) sends every row
+    # to the composed path, the same kernels on the same values as the aligned call with _composed
+    B, GUARD, SENTINEL = 64, 64, 12345.0
+    lib = backend.load_library()
+    dw = gpu._chain_walk(gpu._name_to_idx_map[link])
+    ops_f = gpu._ops_f(dw).detach()
+    walk = backend._walk_struct(dw.program, ops_f, dw.ops_i, gpu._n_dofs)
+
+    def off_by_one(values):
+        flat = torch.full((values.numel() + 1,), -7, device="cuda", dtype=values.dtype)
+        flat[1:] = values.reshape(-1)
+        v = flat[1:].view(values.shape)
+        assert flat.data_ptr() % 16 == 0 and v.data_ptr() % 16 != 0 and v.is_contiguous()
+        return flat, v
+
+    ins = [off_by_one(t[:B]) for t in (q0, tp, tq)]
+    outs = [off_by_one(torch.zeros(B, gpu._n_dofs)), off_by_one(torch.zeros(B, 2)), off_by_one(torch.zeros(B, dtype=torch.int32))]
+    need = int(lib.drm_inverse_kinematics_scratch_floats(ctypes.byref(walk), B))
+    assert need > 0 and int(lib.drm_inverse_kinematics_scratch_floats_aligned(ctypes.byref(walk), B)) <= need
+    scratch = torch.full((need + GUARD,), SENTINEL, device="cuda")
+    lower, upper = gpu._joint_bounds()
+    rc = lib.drm_inverse_kinematics(ctypes.byref(walk), ins[0][1].data_ptr(), ins[1][1].data_ptr(), ins[2][1].data_ptr(), B, 32, 0.01, 1.0,
+                                    1e-4, 1e-3, lower.data_ptr(), upper.data_ptr(), 0, outs[0][1].data_ptr(), outs[1][1].data_ptr(),
+                                    outs[2][1].data_ptr(), scratch.data_ptr(), backend._stream(q0.device))
+    assert rc == 0, lib.drm_last_error()
+    torch.cuda.synchronize()
+    assert bool((scratch[need:] == SENTINEL).all())                 # (the call stayed within the scratch it asked for)
+    assert all(float(flat[0]) == -7 for flat, _ in outs)            # (and wrote nothing in front of its outputs)
+    want = gpu.compute_inverse_kinematics(q0[:B].clone(), link, tp[:B].clone(), tq[:B].clone(), _composed=True)
+    assert (want.iterations > 0).any()
+    assert torch.equal(outs[0][1], want.q) and torch.equal(outs[2][1], want.iterations)
+    assert torch.equal(outs[1][1][:, 0], want.pos_err) and torch.equal(outs[1][1][:, 1], want.rot_err)
 
 
 @pytest.mark.gpu

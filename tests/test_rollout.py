@@ -2,10 +2,16 @@
 DifferentiableRobotModel.compute_forward_dynamics_rollout).
 
 CPU (not gpu): the host build (libdrm_cpu.so) against one compute_forward_dynamics call plus the integrator (T = 1), against a
-rollout composed from the fp64 oracle (T = 50), against rollouts and gradients of the UNMODIFIED reference
+rollout composed from the fp64 oracle (T = 50), against rollouts and gradients of the UNMODIFIED reference for both integrators
 (tests/golden/golden_rollout.npz, made by tests/golden/make_golden_rollout.py), gradients against torch autograd through this
 package's own per-step loop, and the API.  GPU (-m gpu): the fused arm and finger kernels, the composed path and ragged tails
-against the host build and the oracle, a full-size Panda launch, gradients and graph capture.
+against the host build and the oracle at the defaults (semi-implicit Euler, gravity, no damping), a full-size Panda launch, the
+Panda's gradients and graph capture.
+
+What is NOT here is in test_rollout_edges.py: explicit Euler and the flags on the GPU, qdd_traj, pointers that really are misaligned
+and the scratch contract (through the C ABI: the views of check_normalised_views_and_ragged are copied to aligned tensors by the
+binding), gradients against fp64 on every path (worst error 2.3 x the float32 yardstick's on the host build, 1.5 x on the MI355X,
+8 x allowed), and non-finite rows.
 """
 import ctypes
 
@@ -149,19 +155,21 @@ def learnable_mass_model(robot, link, l_value, device="cpu"):
 @pytest.mark.parametrize("robot", GOLDEN_ROBOTS)
 def test_gradients_against_reference_autograd(robot):
     g = load_golden_rollout()
-    m, l = learnable_mass_model(robot, str(g[robot + "/grad/link"]), g[robot + "/grad/l"])
     dt = float(g["dt"])
-    q0, qd0, tau = (torch.tensor(g["%s/%s" % (robot, k)], requires_grad=True) for k in ("q0", "qd0", "tau"))
-    qt, qdt = m.compute_forward_dynamics_rollout(q0, qd0, tau, dt)
-    loss = loss_of(qt, qdt)
-    assert abs(loss.item() - float(g[robot + "/grad/loss"])) <= 1e-4 * abs(float(g[robot + "/grad/loss"]))
-    loss.backward()
-    rtol = 1e-3 if robot in ("panda_no_gripper", "iiwa7") else 1e-2
-    assert grad_close(q0.grad, g[robot + "/grad/q0"], rtol)
-    assert grad_close(qd0.grad, g[robot + "/grad/qd0"], rtol)
-    assert grad_close(tau.grad, g[robot + "/grad/tau"], rtol)
-    ref = g[robot + "/grad/l_grad"]
-    assert abs(float(l.grad) - float(ref)) <= rtol * max(abs(float(ref)), 1e-3 * np.abs(g[robot + "/grad/tau"]).max()), (float(l.grad), float(ref))
+    for pre, integ, grav in (("/grad/", "semi_implicit_euler", True), ("/grad_euler_g0_d0/", "euler", False)):
+        pre = robot + pre
+        m, l = learnable_mass_model(robot, str(g[robot + "/grad/link"]), g[robot + "/grad/l"])
+        q0, qd0, tau = (torch.tensor(g["%s/%s" % (robot, k)], requires_grad=True) for k in ("q0", "qd0", "tau"))
+        qt, qdt = m.compute_forward_dynamics_rollout(q0, qd0, tau, dt, integrator=integ, include_gravity=grav)
+        loss = loss_of(qt, qdt)
+        assert abs(loss.item() - float(g[pre + "loss"])) <= 1e-4 * abs(float(g[pre + "loss"]))
+        loss.backward()
+        rtol = 1e-3 if robot in ("panda_no_gripper", "iiwa7") else 1e-2
+        assert grad_close(q0.grad, g[pre + "q0"], rtol), (robot, integ)
+        assert grad_close(qd0.grad, g[pre + "qd0"], rtol), (robot, integ)
+        assert grad_close(tau.grad, g[pre + "tau"], rtol), (robot, integ)
+        ref = g[pre + "l_grad"]
+        assert abs(float(l.grad) - float(ref)) <= rtol * max(abs(float(ref)), 1e-3 * np.abs(g[pre + "tau"]).max()), (integ, float(l.grad), float(ref))
 
 
 def _grads_through(m, fn, q0, qd0, tau, params):
@@ -266,8 +274,9 @@ def _backend_rollout(m, q0, qd0, tau, dt, explicit=False, want_qdd=True):
                                             want_qdd=want_qdd)
 
 
-def check_misaligned_and_ragged(device):
-    """Misaligned slices and B % 64 != 0 against the aligned, full-tile call at the backend level (rows are independent)."""
+def check_normalised_views_and_ragged(device):
+    """Row slices that backend._dev_f32 copies to aligned tensors, and B % 64 != 0, against the aligned, full-tile call at the backend
+    level (rows are independent).  The C side never sees a misaligned pointer here: test_rollout_edges.py hands it some."""
     for robot in ("panda_no_gripper", "allegro_left", "fetch_arm_no_gripper", "iiwa7_allegro"):
         m = load_model(robot, device)
         n, T, B = m._n_dofs, 5, 128
@@ -275,12 +284,13 @@ def check_misaligned_and_ragged(device):
         tau = torques(m, T, B + 1, scale=0.05)
         full = _backend_rollout(m, torch.from_numpy(q[:B]).to(device), torch.from_numpy(qd[:B]).to(device),
                                 torch.from_numpy(np.ascontiguousarray(tau[:, :B])).to(device), 1e-3)
-        # rows 1 .. B of a [B + 1, n] tensor: a slice whose data pointer is 4 bytes past a 16-byte boundary
+        # rows 1 .. B of a [B + 1, n] tensor: a slice whose data pointer is off a 16-byte boundary (n = 7), and a non-contiguous
+        # slice of tau: the binding clones the first and .reshape copies the second
         qs, qds = torch.from_numpy(np.concatenate([q[-1:], q[:B]])).to(device)[1:], torch.from_numpy(np.concatenate([qd[-1:], qd[:B]])).to(device)[1:]
         ts = torch.from_numpy(np.concatenate([tau[:, -1:], tau[:, :B]], axis=1)).to(device)[:, 1:]
         mis = _backend_rollout(m, qs, qds, ts, 1e-3)
-        # (on the GPU a misaligned call and a ragged tail run other kernels than the full aligned tiles: their rows agree to the
-        # rounding of the two kernels, within twice the rollout tolerance; the host build computes every row the same way)
+        # (on the GPU a ragged tail runs other kernels than the full aligned tiles: their rows agree to the rounding of the two
+        # kernels, within twice the rollout tolerance; the host build computes every row the same way)
         tol = 2 * rollout_tol(robot, 8, 1e-3) if device != "cpu" else 0.0
         for a, b in zip(full[:2], mis[:2]):
             assert rel(b.cpu(), a.cpu()) <= tol, (robot, rel(b.cpu(), a.cpu()))
@@ -291,8 +301,8 @@ def check_misaligned_and_ragged(device):
                 assert rel(b.cpu(), a[:, :rows].cpu()) <= tol, (robot, rows, rel(b.cpu(), a[:, :rows].cpu()))
 
 
-def test_misaligned_and_ragged_cpu():
-    check_misaligned_and_ragged("cpu")
+def test_normalised_views_and_ragged_cpu():
+    check_normalised_views_and_ragged("cpu")
 
 
 # ---------------------------------------------------------------------------------------------------------------------- GPU
@@ -390,5 +400,5 @@ def test_gpu_graph_capture_bit_equal():
 
 
 @pytest.mark.gpu
-def test_gpu_misaligned_and_ragged():
-    check_misaligned_and_ragged("cuda:0")
+def test_gpu_normalised_views_and_ragged():
+    check_normalised_views_and_ragged("cuda:0")
