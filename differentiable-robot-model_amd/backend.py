@@ -28,6 +28,8 @@ ROLLOUT_EXPLICIT_EULER = 4    # include/drm_hip.h DRM_ROLLOUT_EXPLICIT_EULER (AB
 IK_POSITION_ONLY, IK_COMPOSED = 1, 2     # include/drm_hip.h DRM_IK_POSITION_ONLY / DRM_IK_COMPOSED (ABI 15)
 OSC_POSITION_ONLY, OSC_COMPOSED = 8, 16  # include/drm_hip.h DRM_OSC_POSITION_ONLY / DRM_OSC_COMPOSED
 FDD_COMPOSED = 32             # include/drm_hip.h DRM_FDD_COMPOSED
+REGRESSOR_COMPOSED = 64       # include/drm_hip.h DRM_REGRESSOR_COMPOSED
+REGRESSOR_COLS = 10           # columns per body: m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
 
@@ -90,7 +92,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_inverse_kinematics", "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned",
            "drm_operational_space", "drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned",
            "drm_forward_dynamics_derivatives", "drm_forward_dynamics_derivatives_scratch_floats",
-           "drm_forward_dynamics_derivatives_scratch_floats_aligned")
+           "drm_forward_dynamics_derivatives_scratch_floats_aligned",
+           "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -196,6 +199,11 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_forward_dynamics_derivatives.restype = ctypes.c_int
         lib.drm_forward_dynamics_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
         for name in ("drm_forward_dynamics_derivatives_scratch_floats", "drm_forward_dynamics_derivatives_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, i64]
+        lib.drm_rnea_regressor.restype = ctypes.c_int
+        lib.drm_rnea_regressor.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp]
+        for name in ("drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
@@ -1006,6 +1014,30 @@ def forward_dynamics_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, f, incl
                                                     qdd.data_ptr(), dq.data_ptr(), dqd.data_ptr(), minv.data_ptr(),
                                                     scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return qdd, dq, dqd, minv
+
+
+def rnea_regressor(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity: bool, use_damping: bool, n_dofs: int,
+                   composed: bool = False):
+    """Y [B, n, P] with tau = Y phi, P = 10 n_ops (+ n with damping): the inverse-dynamics regressor (include/drm_hip.h
+    drm_rnea_regressor).  ``composed`` forces the general kernel on every row (DRM_REGRESSOR_COMPOSED: tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd, qdd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(qdd, "qdd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B or qdd.shape[0] != B:
+        raise ValueError("q / qd / qdd batch sizes differ")
+    P = REGRESSOR_COLS * prog.n_ops + (n_dofs if use_damping else 0)
+    (Y,) = _outputs(q.device, (B, n_dofs, P))
+    if B == 0:
+        return Y
+    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (REGRESSOR_COMPOSED if composed else 0)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    query = lib.drm_rnea_regressor_scratch_floats if composed else lib.drm_rnea_regressor_scratch_floats_aligned
+    need = int(query(ctypes.byref(walk), B))
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q.device):
+        _check(lib.drm_rnea_regressor(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, Y.data_ptr(),
+                                      scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    return Y
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

@@ -24,6 +24,7 @@
 #include "drm_ik.hpp"
 #include "drm_osc.hpp"
 #include "drm_fdd.hpp"
+#include "drm_regressor.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -218,6 +219,29 @@ void fdd_host_rows(const drm_walk *w, const float *q, const float *qd, const flo
         drm::fdd_solve_columns<float>(n, Hf, wf, [&](int i, int j) { return Dq[i * n + j]; }, [&](int i, int j, float v) { Dq[i * n + j] = v; });
         drm::fdd_solve_columns<float>(n, Hf, wf, [&](int i, int j) { return Dqd[i * n + j]; }, [&](int i, int j, float v) { Dqd[i * n + j] = v; });
         for (int k = 0; k < n; ++k) qdd[b * n + k] = acc[k];
+    }
+}
+// drm_rnea_regressor, rows [b0, b0 + rows): drm_regressor.hpp's walk of the row, its records on this thread's heap
+void regressor_host_rows(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t b0, int64_t rows, int flags, float *Y) {
+    const int n = w->n_dofs, n_ops = w->n_ops;
+    const bool damping = (flags & DRM_RNEA_DAMPING) != 0;
+    const int64_t P = (int64_t)drm::REG_COLS * n_ops + (damping ? n : 0);
+    const Ctl ctl(w);
+    std::vector<float> rec((size_t)3 * (n_ops > 0 ? n_ops : 1));
+    Motion ms[DRM_MAX_SLOTS];
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd + b * n, *qddr = qdd ? qdd + b * n : nullptr;
+        float *Yr = Y + b * n * P;
+        for (int64_t i = 0; i < n * P; ++i) Yr[i] = 0.0f;
+        drm::regressor_tree_walk(
+            n_ops, w->n_segments > 1 ? w->prefix_end : 0, ctl, [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
+            (flags & DRM_RNEA_GRAVITY) ? 9.81f : 0.0f, [&](int d, float &a, float &v, float &acc) { a = qr[d]; v = qdr[d]; acc = qddr ? qddr[d] : 0.0f; },
+            [&](int k, float c, float s, float x) { rec[3 * k] = c; rec[3 * k + 1] = s; rec[3 * k + 2] = x; },
+            [&](int k, float &c, float &s, float &x) { c = rec[3 * k]; s = rec[3 * k + 1]; x = rec[3 * k + 2]; },
+            [&](int sl, const Motion &M) { ms[sl] = M; }, [&](int sl, Motion &M) { M = ms[sl]; },
+            [&](int dof, int op, int col, float v) { Yr[dof * P + drm::REG_COLS * op + col] = v; });
+        if (damping)
+            for (int j = 0; j < n; ++j) Yr[j * P + drm::REG_COLS * n_ops + j] = qdr[j];
     }
 }
 } // namespace
@@ -441,6 +465,23 @@ int drm_forward_dynamics_derivatives(const drm_walk *w, const float *q, const fl
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     const int fl = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { fdd_host_rows(w, q, qd, f, b0, rows, fl, qdd, dq, dqd, minv); });
+    return DRM_OK;
+}
+
+// The inverse-dynamics regressor: every row runs drm_regressor.hpp's walk — the general kernel of drm_regressor.hip without its
+// records in LDS / scratch.  The same walks are refused, with the same message.
+int64_t drm_rnea_regressor_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_rnea_regressor(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y, float *,
+                       void *) {
+    if (int rc = check_walk(w)) return rc;
+    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if ((int64_t)w->n_dofs * (drm::REG_COLS * (int64_t)w->n_ops + w->n_dofs) >= (1 << 24))
+        return fail(DRM_ERR_UNSUPPORTED, "a row of the regressor of this walk has 2^24 entries or more (%ld ops, %ld DoFs)", w->n_ops, w->n_dofs);
+    if (!q || !qd || !Y) return fail(DRM_ERR_INVALID, "q / qd / Y must not be NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { regressor_host_rows(w, q, qd, qdd, b0, rows, flags, Y); });
     return DRM_OK;
 }
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import backend
-from .flatten import (OPF_STRIDE, RobotSpec, WalkProgram, build_robot_spec, build_walk, fold_link_table,
+from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, RobotSpec, WalkProgram, build_robot_spec, build_walk, fold_link_table,
                       foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
                        _ForwardDynamicsRollout, _quat_grad_to_rot)
@@ -1656,6 +1656,67 @@ class DifferentiableRobotModel(torch.nn.Module):
             return backend.forward_dynamics_derivatives(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(),
                                                         f.detach(), bool(include_gravity), bool(use_damping), self._n_dofs,
                                                         composed=composed)
+
+    def compute_inverse_dynamics_regressor(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor,
+                                           include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False, *,
+                                           _composed: bool = False) -> torch.Tensor:
+        """The inverse-dynamics regressor Y [B, n, P] at q, qd, qdd [B, n]: inverse dynamics is linear in the inertial parameters,
+            compute_inverse_dynamics(q, qd, qdd, include_gravity, use_damping) = Y @ inertial_parameters(use_damping)
+        up to float32 rounding.  P = 10 per body of regressor_links(), in that order, each block multiplying
+            [m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz]
+        of the body: c and I in the link's own URDF frame, I about the frame's origin, an off-diagonal column the coefficient of the
+        tied pair Ixy = Iyx.  With ``use_damping`` n more columns follow, Y[b, j, 10 Nb + j] = qd_j: the joint dampings in DoF order.
+        Y[b, j, block i] is zero where body i is not in the sub-tree of joint j.  What closed-form and recursive least-squares
+        identification, adaptive control and excitation-trajectory design need per sample.
+
+        One kernel launch (csrc/drm_regressor.hip): a 7-DoF arm's full 64-row tiles in a kernel that keeps the blocks in registers
+        and stores every tile of Y whole; every other robot a memset of Y and one lane per row with a loop over the bodies.  Argument handling is that of compute_inverse_dynamics
+        (unbatched inputs give an unbatched [n, P]); works for models on the CPU and on a HIP device, and for models with learnable
+        links: their current values are used — Y depends on the kinematic ones — and the links kept for them are bodies of their own.
+        A row whose q, qd or qdd is not finite has non-finite entries and changes no other row.
+
+        The result is computed WITHOUT building an autograd graph and is returned detached, whatever requires grad.  (``_composed``:
+        every row takes the general kernel, DRM_REGRESSOR_COMPOSED; for tests and A/B.)"""
+        return self._compute_inverse_dynamics_regressor(q, qd, qdd, include_gravity, use_damping, bool(_composed))
+
+    @tensor_check
+    def _compute_inverse_dynamics_regressor(self, q, qd, qdd, include_gravity, use_damping, composed):
+        assert q.ndim == 2
+        assert qd.ndim == 2
+        assert qdd.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        assert qd.shape[1] == self._n_dofs
+        assert qdd.shape[1] == self._n_dofs
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            return backend.rnea_regressor(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), qdd.detach(),
+                                          bool(include_gravity), bool(use_damping), self._n_dofs, composed=composed)
+
+    def regressor_links(self) -> List[str]:
+        """The bodies of compute_inverse_dynamics_regressor, in block order: the link of every op of the dynamics walk — the moving
+        links, plus any link kept as an op of its own because it (or a neighbour) is learnable.  Links folded away behind fixed
+        joints are part of their fold target's body (flatten.fold_link_table).  (A link whose joint axis is not +-x / y / z is two
+        ops, and appears twice: the first block, of the massless joint op, multiplies zeros.)"""
+        prog = self._dynamics_walk().program
+        return [self._spec.link_names[int(i)] for i in prog.links[:prog.n_ops]]
+
+    def inertial_parameters(self, use_damping: Optional[bool] = False) -> torch.Tensor:
+        """phi [P]: the parameters compute_inverse_dynamics_regressor's columns multiply, read from the same (folded, current) link
+        table the kernels read — 10 per body of regressor_links(), [m, m c, Ixx, Ixy, Ixz, Iyy, Iyz, Izz] in the link's URDF frame
+        with I about the frame's origin, then with ``use_damping`` the n joint dampings in DoF order.  float32 on the model's
+        device, detached."""
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            prog = dw.program
+            table = self._link_table(dw.fold_key).detach().reshape(-1)
+            rows = prog.gather[:prog.n_ops, OPF_MASS] - OPF_MASS          # flat index of every op's row in the link table
+            take = [OPF_MASS, OPF_MCOM, OPF_MCOM + 1, OPF_MCOM + 2, OPF_IO, OPF_IO + 1, OPF_IO + 2, OPF_IO + 4, OPF_IO + 5, OPF_IO + 8]
+            idx = (rows[:, None] + np.asarray(take, np.int64)[None, :]).reshape(-1)
+            if use_damping:
+                op_of_dof = {int(prog.ops_i[k, 0]): k for k in range(prog.n_ops) if prog.ops_i[k, 0] >= 0}
+                idx = np.concatenate([idx, np.asarray([prog.gather[op_of_dof[d], OPF_DAMP] for d in range(self._n_dofs)], np.int64)])
+            return table.index_select(0, torch.from_numpy(idx).to(table.device)).to(torch.float32)
 
     def compute_forward_dynamics_old(self, q: torch.Tensor, qd: torch.Tensor, f: torch.Tensor,
                                      include_gravity: Optional[bool] = True, use_damping: Optional[bool] = True

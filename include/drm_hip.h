@@ -204,6 +204,8 @@ extern "C" {
 #define DRM_OSC_COMPOSED 16     /* force the composed path on every row (tests, A/B) */
 /* flag of drm_forward_dynamics_derivatives, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
 #define DRM_FDD_COMPOSED 32     /* force the composed path on every row (tests, A/B) */
+/* flags of drm_rnea_regressor, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
+#define DRM_REGRESSOR_COMPOSED 64  /* force the general kernel on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -523,6 +525,38 @@ int64_t drm_forward_dynamics_derivatives_scratch_floats(const drm_walk *walk, in
 int64_t drm_forward_dynamics_derivatives_scratch_floats_aligned(const drm_walk *walk, int64_t B);
 int drm_forward_dynamics_derivatives(const drm_walk *walk, const float *q, const float *qd, const float *f, int64_t B, int32_t flags,
                                      float *qdd, float *dq, float *dqd, float *minv, float *scratch, void *stream);
+
+/*
+ * The inverse-dynamics regressor in one call (additive to ABI 15).  Inverse dynamics is linear in the inertial parameters: with
+ * phi the stacked per-op (m, m c, I_o) — what ops_f holds at DRM_OPF_MASS / DRM_OPF_MCOM / DRM_OPF_IO — tau = Y(q, qd, qdd) phi.
+ * What least-squares and recursive identification, adaptive (Slotine-Li) control and excitation-trajectory design need per sample,
+ * and what a caller otherwise gets from 10 n_ops calls of drm_rnea on unit-parameter copies of the robot.
+ *   q, qd, qdd [B, n] (qdd may be NULL: zeros)  ->  Y [B, n, P], dense, P = 10 n_ops (+ n with DRM_RNEA_DAMPING)
+ *   Block i = columns 10 i .. 10 i + 9 belongs to op i of the walk, in walk order, and multiplies
+ *       [m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz]
+ *   of that op's link: c and I in the link's own URDF frame (the signed permutation of DRM_OPI_PERM is undone as the columns are
+ *   stored), I about the frame's origin (I_c + m S(c) S(c)^T), an off-diagonal column the coefficient of the tied pair Iab = Iba.
+ *   Y[b, j, block i] is zero where op i is not in the sub-tree of joint j, and everywhere for the ops of the static prefix; the zeros
+ *   are written.  With DRM_RNEA_DAMPING Y[b, j, 10 n_ops + j] = qd_j (zero elsewhere): the last n parameters are the joint dampings
+ *   in DoF order.  DRM_RNEA_GRAVITY: the base acceleration (0, 0, +9.81) of drm_rnea.
+ *   Y phi = drm_rnea(q, qd, qdd) with the same flags, up to float32 rounding.
+ * Serial 7-DoF arm chains (DRM_WALK_ARM_CHAIN, capacity 8), full 64-row tiles, 16-byte aligned q / qd / qdd / Y and table: ONE
+ * kernel, a block of four wavefronts per tile, one row per lane, the blocks in registers, the tile of Y assembled in LDS and stored
+ * whole in 16-byte stores (84 B in, 1 960 B out per row, nothing else through HBM).  Every other walk, the ragged tail, misaligned
+ * pointers and DRM_REGRESSOR_COMPOSED: one hipMemsetAsync of those rows of Y, then one lane per row and a loop over the ops that
+ * stores the rows of a body's ancestors.  A row with a non-finite q / qd / qdd gets non-finite entries wherever Y depends on that
+ * input and changes no bit of any other row.
+ *   scratch   drm_rnea_regressor_scratch_floats_aligned floats when q / qd / qdd / Y are 16-byte aligned,
+ *             drm_rnea_regressor_scratch_floats floats otherwise and with DRM_REGRESSOR_COMPOSED: the rows' records between ops where
+ *             64 rows of them do not fit the general kernel's LDS budget (3 n_ops + 12 n_slots floats per row and at most 2 048 tiles
+ *             of 64 rows at a time; 0 for walks of up to 26 ops without branch points — arms, hands: scratch may then be NULL)
+ * DRM_ERR_UNSUPPORTED for a walk whose rows of Y have 2^24 entries or more (n (10 n_ops + n)); DRM_ERR_INVALID for a NULL q / qd / Y
+ * or a negative B; B == 0 returns DRM_OK.  Asynchronous on `stream`, never a host synchronisation, no allocation.
+ */
+int64_t drm_rnea_regressor_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_rnea_regressor(const drm_walk *walk, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y,
+                       float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
