@@ -14,6 +14,7 @@ from .robot_model import (  # noqa: F401
     InverseKinematicsResult,
     OperationalSpaceDynamics,
     ForwardDynamicsDerivatives,
+    LagrangianDynamics,
 )
 
 __version__ = "0.1.0"

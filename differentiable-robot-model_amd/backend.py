@@ -29,6 +29,7 @@ IK_POSITION_ONLY, IK_COMPOSED = 1, 2     # include/drm_hip.h DRM_IK_POSITION_ONL
 OSC_POSITION_ONLY, OSC_COMPOSED = 8, 16  # include/drm_hip.h DRM_OSC_POSITION_ONLY / DRM_OSC_COMPOSED
 FDD_COMPOSED = 32             # include/drm_hip.h DRM_FDD_COMPOSED
 REGRESSOR_COMPOSED = 64       # include/drm_hip.h DRM_REGRESSOR_COMPOSED
+LAGRANGIAN_COMPOSED = 128     # include/drm_hip.h DRM_LAGRANGIAN_COMPOSED
 REGRESSOR_COLS = 10           # columns per body: m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
@@ -93,7 +94,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_operational_space", "drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned",
            "drm_forward_dynamics_derivatives", "drm_forward_dynamics_derivatives_scratch_floats",
            "drm_forward_dynamics_derivatives_scratch_floats_aligned",
-           "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned")
+           "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned",
+           "drm_lagrangian_dynamics", "drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -204,6 +206,11 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_rnea_regressor.restype = ctypes.c_int
         lib.drm_rnea_regressor.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp]
         for name in ("drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, i64]
+        lib.drm_lagrangian_dynamics.restype = ctypes.c_int
+        lib.drm_lagrangian_dynamics.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
+        for name in ("drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
@@ -1038,6 +1045,36 @@ def rnea_regressor(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity:
         _check(lib.drm_rnea_regressor(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, Y.data_ptr(),
                                       scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return Y
+
+
+def lagrangian_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, coriolis_only: bool = False, composed: bool = False):
+    """(H [B, n, n], C [B, n, n], g [B, n]) of H qdd + C qd + g = tau, C the Christoffel matrix (include/drm_hip.h
+    drm_lagrangian_dynamics); with ``coriolis_only`` (None, C, None) from the same launch, the other two neither formed nor stored.
+    ``composed`` (or DRM_LAGRANGIAN_COMPOSED=1 in the environment) forces the general kernel on every row (tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B:
+        raise ValueError("q / qd batch sizes differ")
+    if coriolis_only:
+        H, g = None, None
+        (C,) = _outputs(q.device, (B, n_dofs, n_dofs))
+    else:
+        H, C, g = _outputs(q.device, (B, n_dofs, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs))
+    if B == 0:
+        return H, C, g
+    composed = bool(composed) or os.environ.get("DRM_LAGRANGIAN_COMPOSED") == "1"
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_LAGRANGIAN_COMPOSED takes the general kernel on every row: the size for any pointers)
+    query = lib.drm_lagrangian_dynamics_scratch_floats if composed else lib.drm_lagrangian_dynamics_scratch_floats_aligned
+    need = int(query(ctypes.byref(walk), B))
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q.device):
+        _check(lib.drm_lagrangian_dynamics(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, LAGRANGIAN_COMPOSED if composed else 0,
+                                           H.data_ptr() if H is not None else None, C.data_ptr(),
+                                           g.data_ptr() if g is not None else None,
+                                           scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    return H, C, g
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

@@ -14,8 +14,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <limits>
 #include <thread>
 #include <vector>
 
@@ -25,6 +27,7 @@
 #include "drm_osc.hpp"
 #include "drm_fdd.hpp"
 #include "drm_regressor.hpp"
+#include "drm_lagrangian.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -242,6 +245,33 @@ void regressor_host_rows(const drm_walk *w, const float *q, const float *qd, con
             [&](int dof, int op, int col, float v) { Yr[dof * P + drm::REG_COLS * op + col] = v; });
         if (damping)
             for (int j = 0; j < n; ++j) Yr[j * P + drm::REG_COLS * n_ops + j] = qdr[j];
+    }
+}
+// drm_lagrangian_dynamics, rows [b0, b0 + rows): drm_lagrangian.hpp's walk of the row, its records on this thread's heap
+void lagrangian_host_rows(const drm_walk *w, const float *q, const float *qd, int64_t b0, int64_t rows, float *H, float *C, float *g) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    std::vector<float> rec((size_t)drm::LAG_REC_FLOATS * (n_ops > 0 ? n_ops : 1)), slots((size_t)drm::LAG_SLOT_FLOATS * (n_slots > 0 ? n_slots : 1));
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd + b * n;
+        float *Hr = H ? H + b * n * n : nullptr, *Cr = C ? C + b * n * n : nullptr, *gr = g ? g + b * n : nullptr;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(qr[d], qdr[d]);
+        for (int64_t i = 0; i < n * n; ++i) {
+            if (Hr) Hr[i] = 0.0f;
+            if (Cr) Cr[i] = 0.0f;
+        }
+        drm::lagrangian_tree_walk(
+            n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, ctl, [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
+            [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
+            [&](int k, const float *x) { std::copy(x, x + drm::LAG_REC_FLOATS, rec.begin() + (size_t)drm::LAG_REC_FLOATS * k); },
+            [&](int k, float *x) { std::copy_n(rec.begin() + (size_t)drm::LAG_REC_FLOATS * k, drm::LAG_REC_FLOATS, x); },
+            [&](int s, const float *x) { std::copy(x, x + drm::LAG_SLOT_FLOATS, slots.begin() + (size_t)drm::LAG_SLOT_FLOATS * s); },
+            [&](int s, float *x) { std::copy_n(slots.begin() + (size_t)drm::LAG_SLOT_FLOATS * s, drm::LAG_SLOT_FLOATS, x); },
+            [&](int i, int j, float v) { if (Hr) Hr[i * n + j] = bad ? nan : v; },
+            [&](int i, int j, float v) { if (Cr) Cr[i * n + j] = bad ? nan : v; },
+            [&](int j, float v) { if (gr) gr[j] = bad ? nan : v; });
     }
 }
 } // namespace
@@ -482,6 +512,22 @@ int drm_rnea_regressor(const drm_walk *w, const float *q, const float *qd, const
     if (!q || !qd || !Y) return fail(DRM_ERR_INVALID, "q / qd / Y must not be NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { regressor_host_rows(w, q, qd, qdd, b0, rows, flags, Y); });
+    return DRM_OK;
+}
+
+// H, C and g of the equations of motion: every row runs drm_lagrangian.hpp's walk — the general kernel of drm_lagrangian.hip without its
+// records in LDS / scratch.
+int64_t drm_lagrangian_dynamics_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t, float *H, float *C, float *g, float *,
+                            void *) {
+    if (int rc = check_walk(w)) return rc;
+    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
+    if (!H && !C && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { lagrangian_host_rows(w, q, qd, b0, rows, H, C, g); });
     return DRM_OK;
 }
 

@@ -125,6 +125,14 @@ class ForwardDynamicsDerivatives(NamedTuple):
     minv: torch.Tensor                  # [B, n, n] H(q)^-1 = d qdd / d f, symmetric
 
 
+class LagrangianDynamics(NamedTuple):
+    """What DifferentiableRobotModel.compute_lagrangian_dynamics returns (no autograd history on any field): the terms of
+    H(q) qdd + C(q, qd) qd + g(q) = tau."""
+    inertia: torch.Tensor               # [B, n, n] H(q) = compute_lagrangian_inertia_matrix(q)
+    coriolis: torch.Tensor              # [B, n, n] the Christoffel matrix C(q, qd): dH/dt = C + C^T
+    gravity: torch.Tensor               # [B, n] g(q) = compute_inverse_dynamics(q, 0, 0, include_gravity=True, use_damping=False)
+
+
 class DifferentiableRobotModel(torch.nn.Module):
     """Batched FK / geometric Jacobian / RNEA on MI355X behind the reference API."""
 
@@ -1692,6 +1700,49 @@ class DifferentiableRobotModel(torch.nn.Module):
             dw = self._dynamics_walk()
             return backend.rnea_regressor(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), qdd.detach(),
                                           bool(include_gravity), bool(use_damping), self._n_dofs, composed=composed)
+
+    def compute_lagrangian_dynamics(self, q: torch.Tensor, qd: torch.Tensor, *, _composed: bool = False) -> LagrangianDynamics:
+        """The terms of the equations of motion  H(q) qdd + C(q, qd) qd + g(q) = tau  at q, qd [B, n], separately:
+            inertia   [B, n, n]  compute_lagrangian_inertia_matrix(q), up to float32 rounding; symmetric to the bit
+            coriolis  [B, n, n]  the Christoffel matrix, C[i, j] = sum_k Gamma_ijk qd_k with
+                                 Gamma_ijk = (dH_ij/dq_k + dH_ik/dq_j - dH_jk/dq_i) / 2
+            gravity   [B, n]     compute_inverse_dynamics(q, 0, 0, include_gravity=True, use_damping=False)
+        so that C qd + g = compute_non_linear_effects(q, qd, True, False) and dH/dt = C + C^T: dH/dt - 2 C is skew-symmetric, which
+        passivity-based and adaptive controllers (tau = H a + C v + g - K s with v != qd) rely on, as generalised-momentum observers
+        do on pdot = tau + C^T qd - g + tau_ext with p = H qd.  The product C qd does not determine C; this is the one choice with
+        those properties.  Joint damping is NOT part of C:  tau = H qdd + C qd + g + damping * qd.  H[i, j] and C[i, j] are exactly
+        zero where joints i and j lie on different branches.
+
+        One kernel launch (csrc/drm_lagrangian.hip): one sweep out and one back over the tree instead of dH/dq by n (n + 1) / 2
+        backward passes through the inertia matrix.  A 7-DoF arm's full 64-row tiles run a kernel that keeps everything in registers and stores
+        the tiles of H, C and g whole; every other robot one lane per row over the ops of its walk.  With the robot's own
+        constant-folded kernels attached this entry point still runs the library kernels.  Argument handling is that of
+        compute_forward_dynamics_derivatives (unbatched inputs give unbatched results); works for models on the CPU and on a HIP
+        device, with either joint model (reference_compat) and for models with learnable links: their current values are used.
+        A row whose q or qd is not finite — or whose |q| is beyond 1e5, where float32 no longer resolves an angle — returns NaN
+        and changes no bit of any other row.
+
+        The results carry NO autograd history, whatever requires grad.  (``_composed``, or DRM_LAGRANGIAN_COMPOSED=1 in the
+        environment: every row takes the general kernel, DRM_LAGRANGIAN_COMPOSED; for tests and A/B measurements.)"""
+        return LagrangianDynamics(*self._compute_lagrangian_dynamics(q, qd, False, bool(_composed)))
+
+    def compute_coriolis_matrix(self, q: torch.Tensor, qd: torch.Tensor) -> torch.Tensor:
+        """compute_lagrangian_dynamics(q, qd).coriolis [B, n, n] alone, to the bit: the same launch with the other two outputs
+        neither formed (7-DoF arms) nor written."""
+        return self._compute_lagrangian_dynamics(q, qd, True, False)[1]
+
+    @tensor_check
+    def _compute_lagrangian_dynamics(self, q, qd, coriolis_only, composed):
+        assert q.ndim == 2
+        assert qd.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        assert qd.shape[1] == self._n_dofs
+        assert q.shape[0] == qd.shape[0]
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            return backend.lagrangian_dynamics(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), self._n_dofs,
+                                               coriolis_only=coriolis_only, composed=composed)
 
     def regressor_links(self) -> List[str]:
         """The bodies of compute_inverse_dynamics_regressor, in block order: the link of every op of the dynamics walk — the moving

@@ -206,6 +206,8 @@ extern "C" {
 #define DRM_FDD_COMPOSED 32     /* force the composed path on every row (tests, A/B) */
 /* flags of drm_rnea_regressor, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
 #define DRM_REGRESSOR_COMPOSED 64  /* force the general kernel on every row (tests, A/B) */
+/* flag of drm_lagrangian_dynamics */
+#define DRM_LAGRANGIAN_COMPOSED 128 /* force the general kernel on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -557,6 +559,39 @@ int64_t drm_rnea_regressor_scratch_floats(const drm_walk *walk, int64_t B);
 int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *walk, int64_t B);
 int drm_rnea_regressor(const drm_walk *walk, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y,
                        float *scratch, void *stream);
+
+/*
+ * The terms of  H(q) qdd + C(q, qd) qd + g(q) = tau  in one call (additive to ABI 15): the joint-space inertia matrix, the Coriolis
+ * matrix and the gravity torques.  What passivity-based and adaptive control (tau = H a + C v + g - K s, v != qd), generalised-momentum
+ * observers (pdot = tau + C^T qd - g + tau_ext, p = H qd) and Lagrangian model learning need, and what a caller otherwise gets from
+ * dH/dq by n (n + 1) / 2 backward passes through drm_crba.
+ *   q, qd [B, n]  ->  H [B, n, n], C [B, n, n], g [B, n]; any of the three may be NULL (not computed where that is cheap, not stored)
+ *   H   what drm_crba returns, up to float32 rounding; symmetric to the bit
+ *   g   drm_rnea(q, 0, 0, DRM_RNEA_GRAVITY): the torques that hold the robot still under the base acceleration (0, 0, +9.81)
+ *   C   the CHRISTOFFEL matrix, C[i, j] = sum_k Gamma_ijk qd_k, Gamma_ijk = (dH_ij/dq_k + dH_ik/dq_j - dH_jk/dq_i) / 2: the one C with
+ *       C qd + g = drm_rnea(q, qd, 0, DRM_RNEA_GRAVITY) for which dH/dt = C + C^T (dH/dt - 2 C skew-symmetric).  Joint damping is not
+ *       part of C: tau = H qdd + C qd + g + damping * qd.
+ *   H[i, j] and C[i, j] are exact zeros where joints i and j lie on different branches; the zeros are written.
+ * One sweep over the tree (Echeandia and Wensing 2021, csrc/drm_lagrangian.hpp), every quantity in its link's own frame.  Serial 7-DoF
+ * arm chains (DRM_WALK_ARM_CHAIN, capacity 8), full 64-row tiles, 16-byte aligned q / qd / H / C / g and table: ONE kernel, one
+ * wavefront per tile, one row per lane, everything in registers, the tiles of H, C and g assembled in LDS and stored whole in 16-byte
+ * stores (56 B in, 420 B out per row, nothing else through HBM; with H and g NULL 196 B out and neither is formed).  Every other walk,
+ * the ragged tail, misaligned pointers and DRM_LAGRANGIAN_COMPOSED: one hipMemsetAsync of those rows of H and of C, then one lane per
+ * row and two loops over the ops that store the entries between a joint and its ancestors.  A walk that carries its robot's own code
+ * object runs these library kernels all the same.
+ * A row with a q or qd that is not finite, or with a |q| beyond 1e5 (float32 no longer resolves such an angle), gets NaN in every
+ * entry that is written and changes no bit of any other row.
+ *   scratch   drm_lagrangian_dynamics_scratch_floats_aligned floats when q / qd / H / C / g are 16-byte aligned,
+ *             drm_lagrangian_dynamics_scratch_floats floats otherwise and with DRM_LAGRANGIAN_COMPOSED: the rows' records between the
+ *             sweeps where 64 rows of them do not fit the general kernel's LDS budget (12 n_ops + 22 n_slots floats per row and at
+ *             most 2 048 tiles of 64 rows at a time; 0 for chains of up to 10 ops: scratch may then be NULL)
+ * DRM_ERR_INVALID for a NULL q / qd, for H, C and g all NULL, or a negative B; B == 0 returns DRM_OK.  Asynchronous on `stream`, never
+ * a host synchronisation, no allocation.
+ */
+int64_t drm_lagrangian_dynamics_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_lagrangian_dynamics(const drm_walk *walk, const float *q, const float *qd, int64_t B, int32_t flags, float *H, float *C, float *g,
+                            float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
