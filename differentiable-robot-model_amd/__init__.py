@@ -15,6 +15,7 @@ from .robot_model import (  # noqa: F401
     OperationalSpaceDynamics,
     ForwardDynamicsDerivatives,
     LagrangianDynamics,
+    InverseDynamicsDerivatives,
 )
 
 __version__ = "0.1.0"

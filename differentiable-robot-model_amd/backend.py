@@ -30,6 +30,7 @@ OSC_POSITION_ONLY, OSC_COMPOSED = 8, 16  # include/drm_hip.h DRM_OSC_POSITION_ON
 FDD_COMPOSED = 32             # include/drm_hip.h DRM_FDD_COMPOSED
 REGRESSOR_COMPOSED = 64       # include/drm_hip.h DRM_REGRESSOR_COMPOSED
 LAGRANGIAN_COMPOSED = 128     # include/drm_hip.h DRM_LAGRANGIAN_COMPOSED
+IDD_COMPOSED = 256            # include/drm_hip.h DRM_IDD_COMPOSED
 REGRESSOR_COLS = 10           # columns per body: m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
@@ -95,7 +96,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_forward_dynamics_derivatives", "drm_forward_dynamics_derivatives_scratch_floats",
            "drm_forward_dynamics_derivatives_scratch_floats_aligned",
            "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned",
-           "drm_lagrangian_dynamics", "drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned")
+           "drm_lagrangian_dynamics", "drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned",
+           "drm_rnea_derivatives", "drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -211,6 +213,11 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_lagrangian_dynamics.restype = ctypes.c_int
         lib.drm_lagrangian_dynamics.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
         for name in ("drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, i64]
+        lib.drm_rnea_derivatives.restype = ctypes.c_int
+        lib.drm_rnea_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
+        for name in ("drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
@@ -1075,6 +1082,33 @@ def lagrangian_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, cor
                                            g.data_ptr() if g is not None else None,
                                            scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return H, C, g
+
+
+def rnea_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity: bool, use_damping: bool, n_dofs: int,
+                     composed: bool = False):
+    """(tau [B, n], dtau_dq [B, n, n], dtau_dqd [B, n, n], H [B, n, n]): inverse dynamics and its first-order derivatives at
+    (q, qd, qdd), [b, i, j] = d tau_i / d x_j (include/drm_hip.h drm_rnea_derivatives).  ``composed`` (or DRM_IDD_COMPOSED=1 in the
+    environment) forces the general kernel on every row (tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd, qdd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(qdd, "qdd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B or qdd.shape[0] != B:
+        raise ValueError("q / qd / qdd batch sizes differ")
+    tau, dq, dqd, H = _outputs(q.device, (B, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs))
+    if B == 0:
+        return tau, dq, dqd, H
+    composed = bool(composed) or os.environ.get("DRM_IDD_COMPOSED") == "1"
+    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (IDD_COMPOSED if composed else 0)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_IDD_COMPOSED takes the general kernel on every row: the size for any pointers)
+    query = lib.drm_rnea_derivatives_scratch_floats if composed else lib.drm_rnea_derivatives_scratch_floats_aligned
+    need = int(query(ctypes.byref(walk), B))
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    with _on_device(q.device):
+        _check(lib.drm_rnea_derivatives(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, tau.data_ptr(),
+                                        dq.data_ptr(), dqd.data_ptr(), H.data_ptr(),
+                                        scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    return tau, dq, dqd, H
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

@@ -28,6 +28,7 @@
 #include "drm_fdd.hpp"
 #include "drm_regressor.hpp"
 #include "drm_lagrangian.hpp"
+#include "drm_idd.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -272,6 +273,33 @@ void lagrangian_host_rows(const drm_walk *w, const float *q, const float *qd, in
             [&](int i, int j, float v) { if (Hr) Hr[i * n + j] = bad ? nan : v; },
             [&](int i, int j, float v) { if (Cr) Cr[i * n + j] = bad ? nan : v; },
             [&](int j, float v) { if (gr) gr[j] = bad ? nan : v; });
+    }
+}
+// drm_rnea_derivatives, rows [b0, b0 + rows): drm_idd.hpp's walk of the row, its records on this thread's heap
+void idd_host_rows(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t b0, int64_t rows, int flags, float *tau,
+                   float *dq, float *dqd, float *H) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    std::vector<float> rec((size_t)drm::IDD_REC_FLOATS * (n_ops > 0 ? n_ops : 1)), slots((size_t)drm::IDD_SLOT_FLOATS * (n_slots > 0 ? n_slots : 1));
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd + b * n, *qddr = qdd + b * n;
+        float *tr = tau ? tau + b * n : nullptr;
+        float *Mr[3] = {dq ? dq + b * n * n : nullptr, dqd ? dqd + b * n * n : nullptr, H ? H + b * n * n : nullptr};
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::idd_bad_input(qr[d], qdr[d], qddr[d]);
+        for (float *M : Mr)
+            if (M) std::fill(M, M + (size_t)n * n, 0.0f);
+        drm::idd_tree_walk(
+            n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, (flags & DRM_RNEA_GRAVITY) ? 9.81f : 0.0f, (flags & DRM_RNEA_DAMPING) != 0, ctl,
+            [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
+            [&](int d, float &a, float &v, float &acc) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; acc = bad ? 0.0f : qddr[d]; },
+            [&](int k, const float *x) { std::copy(x, x + drm::IDD_REC_FLOATS, rec.begin() + (size_t)drm::IDD_REC_FLOATS * k); },
+            [&](int k, float *x) { std::copy_n(rec.begin() + (size_t)drm::IDD_REC_FLOATS * k, drm::IDD_REC_FLOATS, x); },
+            [&](int s, const float *x) { std::copy(x, x + drm::IDD_SLOT_FLOATS, slots.begin() + (size_t)drm::IDD_SLOT_FLOATS * s); },
+            [&](int s, float *x) { std::copy_n(slots.begin() + (size_t)drm::IDD_SLOT_FLOATS * s, drm::IDD_SLOT_FLOATS, x); },
+            [&](int which, int i, int j, float v) { if (Mr[which]) Mr[which][i * n + j] = bad ? nan : v; },
+            [&](int j, float v) { if (tr) tr[j] = bad ? nan : v; });
     }
 }
 } // namespace
@@ -528,6 +556,22 @@ int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const float *qd, 
     if (!H && !C && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { lagrangian_host_rows(w, q, qd, b0, rows, H, C, g); });
+    return DRM_OK;
+}
+
+// Inverse dynamics and its first-order derivatives: every row runs drm_idd.hpp's walk — the general kernel of drm_idd.hip without its
+// records in LDS / scratch.
+int64_t drm_rnea_derivatives_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_rnea_derivatives_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_rnea_derivatives(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau, float *dq,
+                         float *dqd, float *H, float *, void *) {
+    if (int rc = check_walk(w)) return rc;
+    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (!q || !qd || !qdd) return fail(DRM_ERR_INVALID, "q / qd / qdd must not be NULL");
+    if (!tau && !dq && !dqd && !H) return fail(DRM_ERR_INVALID, "every output is NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { idd_host_rows(w, q, qd, qdd, b0, rows, flags, tau, dq, dqd, H); });
     return DRM_OK;
 }
 

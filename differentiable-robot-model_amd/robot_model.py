@@ -133,6 +133,15 @@ class LagrangianDynamics(NamedTuple):
     gravity: torch.Tensor               # [B, n] g(q) = compute_inverse_dynamics(q, 0, 0, include_gravity=True, use_damping=False)
 
 
+class InverseDynamicsDerivatives(NamedTuple):
+    """What DifferentiableRobotModel.compute_inverse_dynamics_derivatives returns (no autograd history on any field);
+    [b, i, j] = d tau_i / d x_j."""
+    tau: torch.Tensor                   # [B, n] = compute_inverse_dynamics(q, qd, qdd, ...)
+    dtau_dq: torch.Tensor               # [B, n, n] (damping never enters it)
+    dtau_dqd: torch.Tensor              # [B, n, n] (with use_damping it includes diag(damping); gravity never enters it)
+    dtau_dqdd: torch.Tensor             # [B, n, n] H(q), symmetric to the bit
+
+
 class DifferentiableRobotModel(torch.nn.Module):
     """Batched FK / geometric Jacobian / RNEA on MI355X behind the reference API."""
 
@@ -1743,6 +1752,47 @@ class DifferentiableRobotModel(torch.nn.Module):
             dw = self._dynamics_walk()
             return backend.lagrangian_dynamics(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), self._n_dofs,
                                                coriolis_only=coriolis_only, composed=composed)
+
+    def compute_inverse_dynamics_derivatives(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor,
+                                             include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False, *,
+                                             _composed: bool = False) -> InverseDynamicsDerivatives:
+        """Inverse dynamics tau = ID(q, qd, qdd) and its first-order derivatives at q, qd, qdd [B, n]: what inverse-dynamics
+        trajectory optimisation (direct transcription with torque limits) needs at every knot, and gain design for computed-torque
+        control, an EKF with a torque measurement and Gauss-Newton identification in the state:
+            tau        [B, n]     compute_inverse_dynamics(q, qd, qdd, include_gravity, use_damping)
+            dtau_dq    [B, n, n]  [b, i, j] = d tau_i / d q_j    (damping never enters it)
+            dtau_dqd   [B, n, n]  [b, i, j] = d tau_i / d qd_j   (with ``use_damping`` it includes diag(damping); gravity never enters it)
+            dtau_dqdd  [B, n, n]  H(q) = compute_lagrangian_inertia_matrix(q), up to float32 rounding; symmetric to the bit
+        Entries of the three matrices are exactly zero where joints i and j lie on different branches.
+
+        One kernel launch (csrc/drm_idd.hip): one sweep out and one back over the tree (Carpentier and Mansard 2018; Singh, Russell
+        and Wensing 2022), O(n depth) work, instead of n backward passes through compute_inverse_dynamics and an inertia-matrix call.
+        A 7-DoF arm's full 64-row tiles run a kernel that keeps everything in registers and stores the tiles of the outputs whole; every
+        other robot one lane per row over the ops of its walk.  With the robot's own constant-folded kernels attached this entry point
+        still runs the library kernels.  Argument handling is that of compute_forward_dynamics_derivatives (unbatched inputs give
+        unbatched results); works for models on the CPU and on a HIP device, with either joint model (reference_compat) and for
+        models with learnable links: their current values are used.  A row whose q, qd or qdd is not finite — or whose |q| is
+        beyond 1e5, where float32 no longer resolves an angle — returns NaN and changes no bit of any other row.
+
+        The results carry NO autograd history, whatever requires grad.  (``_composed``, or DRM_IDD_COMPOSED=1 in the environment:
+        every row takes the general kernel, DRM_IDD_COMPOSED; for tests and A/B measurements.)"""
+        return InverseDynamicsDerivatives(*self._compute_inverse_dynamics_derivatives(q, qd, qdd, include_gravity, use_damping,
+                                                                                      bool(_composed)))
+
+    @tensor_check
+    def _compute_inverse_dynamics_derivatives(self, q, qd, qdd, include_gravity, use_damping, composed):
+        assert q.ndim == 2
+        assert qd.ndim == 2
+        assert qdd.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        assert qd.shape[1] == self._n_dofs
+        assert qdd.shape[1] == self._n_dofs
+        assert q.shape[0] == qd.shape[0] == qdd.shape[0]
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            return backend.rnea_derivatives(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), qdd.detach(),
+                                            bool(include_gravity), bool(use_damping), self._n_dofs, composed=composed)
 
     def regressor_links(self) -> List[str]:
         """The bodies of compute_inverse_dynamics_regressor, in block order: the link of every op of the dynamics walk — the moving

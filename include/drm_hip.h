@@ -208,6 +208,8 @@ extern "C" {
 #define DRM_REGRESSOR_COMPOSED 64  /* force the general kernel on every row (tests, A/B) */
 /* flag of drm_lagrangian_dynamics */
 #define DRM_LAGRANGIAN_COMPOSED 128 /* force the general kernel on every row (tests, A/B) */
+/* flag of drm_rnea_derivatives, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
+#define DRM_IDD_COMPOSED 256        /* force the general kernel on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -592,6 +594,39 @@ int64_t drm_lagrangian_dynamics_scratch_floats(const drm_walk *walk, int64_t B);
 int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *walk, int64_t B);
 int drm_lagrangian_dynamics(const drm_walk *walk, const float *q, const float *qd, int64_t B, int32_t flags, float *H, float *C, float *g,
                             float *scratch, void *stream);
+
+/*
+ * Inverse dynamics and its first-order derivatives in one call (additive to ABI 15): tau = ID(q, qd, qdd) and the partial derivatives
+ * of tau with respect to q, qd and qdd.  What inverse-dynamics trajectory optimisation needs at every knot, and gain design for
+ * computed-torque control, an EKF with a torque measurement and Gauss-Newton identification in the state; what a caller otherwise gets
+ * from n backward passes through drm_rnea with one-hot cotangents plus drm_crba.
+ *   q, qd, qdd [B, n]  ->  tau [B, n], dtau_dq [B, n, n], dtau_dqd [B, n, n], H [B, n, n];  [b, i, j] = d tau_i / d x_j;
+ *   any of the four may be NULL (not stored; not formed where that is cheap)
+ *   tau        what drm_rnea returns with the same DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING flags, up to float32 rounding
+ *   H          d tau / d qdd: what drm_crba returns, up to float32 rounding; symmetric to the bit
+ *   dtau_dqd   with DRM_RNEA_DAMPING it includes diag(damping); gravity never enters it
+ *   dtau_dq    damping never enters it
+ *   Entries of the three matrices are exact zeros where joints i and j lie on different branches; the zeros are written.
+ * One sweep out and one back over the tree (Carpentier and Mansard 2018; Singh, Russell and Wensing 2022; csrc/drm_idd.hpp), every
+ * quantity in its link's own frame, O(n depth) work.  Serial 7-DoF arm chains (DRM_WALK_ARM_CHAIN, capacity 8), full 64-row tiles,
+ * 16-byte aligned pointers and table: ONE kernel, one wavefront per tile, one row per lane, everything in registers, the tiles of the
+ * outputs assembled in LDS and stored whole in 16-byte stores (84 B in, 616 B out per row, nothing else through HBM).  Every other walk,
+ * the ragged tail, misaligned pointers and DRM_IDD_COMPOSED: one hipMemsetAsync of those rows of each matrix, then one lane per row and
+ * two loops over the ops that store the entries between a joint and its ancestors.  A walk that carries its robot's own code object
+ * runs these library kernels all the same.
+ * A row with a q, qd or qdd that is not finite, or with a |q| beyond 1e5 (float32 no longer resolves such an angle), gets NaN in every
+ * entry that is written and changes no bit of any other row.
+ *   scratch   drm_rnea_derivatives_scratch_floats_aligned floats when every pointer is 16-byte aligned,
+ *             drm_rnea_derivatives_scratch_floats floats otherwise and with DRM_IDD_COMPOSED: the rows' records between the sweeps
+ *             where 64 rows of them do not fit the general kernel's LDS budget (15 n_ops + 28 n_slots floats per row and at most
+ *             2 048 tiles of 64 rows at a time; 0 for chains of up to 8 ops: scratch may then be NULL)
+ * DRM_ERR_INVALID for a NULL q / qd / qdd, for all four outputs NULL, or a negative B; B == 0 returns DRM_OK.  Asynchronous on
+ * `stream`, never a host synchronisation, no allocation.
+ */
+int64_t drm_rnea_derivatives_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_rnea_derivatives_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_rnea_derivatives(const drm_walk *walk, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau,
+                         float *dtau_dq, float *dtau_dqd, float *H, float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
