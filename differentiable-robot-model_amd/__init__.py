@@ -16,6 +16,8 @@ from .robot_model import (  # noqa: F401
     ForwardDynamicsDerivatives,
     LagrangianDynamics,
     InverseDynamicsDerivatives,
+    EnergyDerivatives,
+    Energy,
 )
 
 __version__ = "0.1.0"

@@ -9,6 +9,7 @@ here one node per public method:
     _InverseDynamics  compute_inverse_dynamics / compute_non_linear_effects           drm_rnea / drm_rnea_backward
     _MassMatrix       compute_lagrangian_inertia_matrix                               drm_crba / drm_rnea_backward per column
     _ForwardDynamics  compute_forward_dynamics (implicit differentiation)             drm_forward_dynamics / drm_rnea_backward
+    _Energy           compute_energy (T, V and their gradients from ONE launch; first order only)          drm_energy
     _FirstOrderOnly   marks the gradients of _FkMse computed under create_graph=True (differentiating through them raises)
     _GradLaunch       a first-order gradient launch as a differentiable node (create_graph=True: second derivatives with respect to
                       q / qd / qdd / f, the output cotangents and — round 6 — the walk's table, i.e. the learnable link parameters)
@@ -697,3 +698,29 @@ class _ForwardDynamicsRollout(torch.autograd.Function):
             with torch.enable_grad():
                 out = [_RolloutFirstOrderOnly.apply(g.requires_grad_(True)) if g is not None else None for g in out]
         return tuple(out) + (None,) * 7
+
+
+class _Energy(torch.autograd.Function):
+    """(T [B], V [B]) = the kinetic and potential energy at q, qd [B, n] (backend.energy, csrc/drm_energy.hip).  The forward launch
+    hands out the gradients with the energies — p = dT/dqd, dT/dq and g = dV/dq — so the backward launches nothing:
+        grad_q = gT[:, None] * dT_dq + gV[:, None] * g,      grad_qd = gT[:, None] * p.
+    First order only (once_differentiable): a second backward through it raises.  The walk's table is a constant of the node: no
+    history flows to learnable link parameters."""
+
+    @staticmethod
+    def forward(ctx, q, qd, prog, ops_f, ops_i, n_dofs):
+        T, V, p, dT_dq, g = backend.energy(prog, ops_f, ops_i, q.detach(), qd.detach(), n_dofs)
+        ctx.save_for_backward(p, dT_dq, g)
+        ctx.dtypes = (q.dtype, qd.dtype)
+        return T, V
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gT, gV):
+        p, dT_dq, g = ctx.saved_tensors
+        grad_q = grad_qd = None
+        if ctx.needs_input_grad[0]:
+            grad_q = (gT[:, None] * dT_dq + gV[:, None] * g).to(ctx.dtypes[0])
+        if ctx.needs_input_grad[1]:
+            grad_qd = (gT[:, None] * p).to(ctx.dtypes[1])
+        return grad_q, grad_qd, None, None, None, None

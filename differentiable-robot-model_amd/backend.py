@@ -31,6 +31,7 @@ FDD_COMPOSED = 32             # include/drm_hip.h DRM_FDD_COMPOSED
 REGRESSOR_COMPOSED = 64       # include/drm_hip.h DRM_REGRESSOR_COMPOSED
 LAGRANGIAN_COMPOSED = 128     # include/drm_hip.h DRM_LAGRANGIAN_COMPOSED
 IDD_COMPOSED = 256            # include/drm_hip.h DRM_IDD_COMPOSED
+ENERGY_COMPOSED = 512         # include/drm_hip.h DRM_ENERGY_COMPOSED
 REGRESSOR_COLS = 10           # columns per body: m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
@@ -97,7 +98,8 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_forward_dynamics_derivatives_scratch_floats_aligned",
            "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned",
            "drm_lagrangian_dynamics", "drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned",
-           "drm_rnea_derivatives", "drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned")
+           "drm_rnea_derivatives", "drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned",
+           "drm_energy", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -218,6 +220,11 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_rnea_derivatives.restype = ctypes.c_int
         lib.drm_rnea_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
         for name in ("drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, i64]
+        lib.drm_energy.restype = ctypes.c_int
+        lib.drm_energy.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
@@ -1109,6 +1116,40 @@ def rnea_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravit
                                         dq.data_ptr(), dqd.data_ptr(), H.data_ptr(),
                                         scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return tau, dq, dqd, H
+
+
+ENERGY_OUTPUTS = ("kinetic", "potential", "momentum", "dkinetic_dq", "gravity")
+
+
+def energy(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, want=ENERGY_OUTPUTS, composed: bool = False):
+    """(T [B], V [B], p [B, n], dT_dq [B, n], g [B, n]): the kinetic and potential energy, the generalised momentum p = H qd and the
+    gradients dT/dq and dV/dq of one launch (include/drm_hip.h drm_energy).  ``want`` names the outputs to compute (ENERGY_OUTPUTS);
+    the others come back as None, neither stored nor, where that saves work, formed.  ``composed`` (or DRM_ENERGY_COMPOSED=1 in the
+    environment) forces the general kernel on every row (tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B:
+        raise ValueError("q / qd batch sizes differ")
+    want = tuple(want)
+    if not want or any(w not in ENERGY_OUTPUTS for w in want):
+        raise ValueError("want must name at least one of %s" % (ENERGY_OUTPUTS,))
+    shapes = {"kinetic": (B,), "potential": (B,), "momentum": (B, n_dofs), "dkinetic_dq": (B, n_dofs), "gravity": (B, n_dofs)}
+    made = dict(zip(want, _outputs(q.device, *[shapes[w] for w in want])))
+    outs = tuple(made.get(name) for name in ENERGY_OUTPUTS)
+    if B == 0:
+        return outs
+    composed = bool(composed) or os.environ.get("DRM_ENERGY_COMPOSED") == "1"
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_ENERGY_COMPOSED takes the general kernel on every row: the size for any pointers)
+    query = lib.drm_energy_scratch_floats if composed else lib.drm_energy_scratch_floats_aligned
+    need = int(query(ctypes.byref(walk), B))
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_energy(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, ENERGY_COMPOSED if composed else 0,
+                              *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
+    return outs
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

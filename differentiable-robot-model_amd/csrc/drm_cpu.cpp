@@ -29,6 +29,7 @@
 #include "drm_regressor.hpp"
 #include "drm_lagrangian.hpp"
 #include "drm_idd.hpp"
+#include "drm_energy.hpp"
 #include "drm_rollout.hpp"
 
 namespace {
@@ -302,6 +303,37 @@ void idd_host_rows(const drm_walk *w, const float *q, const float *qd, const flo
             [&](int j, float v) { if (tr) tr[j] = bad ? nan : v; });
     }
 }
+// drm_energy, rows [b0, b0 + rows): drm_energy.hpp's walk of the row, its records on this thread's heap
+void energy_host_rows(const drm_walk *w, const float *q, const float *qd, int64_t b0, int64_t rows, float *T, float *V, float *p, float *dT,
+                      float *g) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    std::vector<float> rec((size_t)drm::ENERGY_REC_FLOATS * (n_ops > 0 ? n_ops : 1)), slots((size_t)drm::ENERGY_SLOT_FLOATS * (n_slots > 0 ? n_slots : 1));
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd + b * n;
+        float *pr = p ? p + b * n : nullptr, *dr = dT ? dT + b * n : nullptr, *gr = g ? g + b * n : nullptr;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(qr[d], qdr[d]);
+        drm::energy_tree_walk(
+            n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, p || dT || g, ctl, [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
+            [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
+            [&](int k, const float *x) { std::copy(x, x + drm::ENERGY_REC_FLOATS, rec.begin() + (size_t)drm::ENERGY_REC_FLOATS * k); },
+            [&](int k, float *x) { std::copy_n(rec.begin() + (size_t)drm::ENERGY_REC_FLOATS * k, drm::ENERGY_REC_FLOATS, x); },
+            [&](int s, const float *x) { std::copy(x, x + drm::ENERGY_SLOT_FLOATS, slots.begin() + (size_t)drm::ENERGY_SLOT_FLOATS * s); },
+            [&](int s, float *x) { std::copy_n(slots.begin() + (size_t)drm::ENERGY_SLOT_FLOATS * s, drm::ENERGY_SLOT_FLOATS, x); },
+            [&](float Tv, float Vv) {
+                if (T) T[b] = bad ? nan : Tv;
+                if (V) V[b] = bad ? nan : Vv;
+            },
+            [&](int j, float pj, float dj, float gj) {
+                if (j >= n) return;
+                if (pr) pr[j] = bad ? nan : pj;
+                if (dr) dr[j] = bad ? nan : dj;
+                if (gr) gr[j] = bad ? nan : gj;
+            });
+    }
+}
 } // namespace
 
 extern "C" {
@@ -572,6 +604,21 @@ int drm_rnea_derivatives(const drm_walk *w, const float *q, const float *qd, con
     if (!tau && !dq && !dqd && !H) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { idd_host_rows(w, q, qd, qdd, b0, rows, flags, tau, dq, dqd, H); });
+    return DRM_OK;
+}
+
+// T, V, p, dT/dq and g: every row runs drm_energy.hpp's walk — the general kernel of drm_energy.hip without its records in LDS / scratch.
+int64_t drm_energy_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_energy_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_energy(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t, float *T, float *V, float *p, float *dT, float *g,
+               float *, void *) {
+    if (int rc = check_walk(w)) return rc;
+    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
+    if (!T && !V && !p && !dT && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { energy_host_rows(w, q, qd, b0, rows, T, V, p, dT, g); });
     return DRM_OK;
 }
 

@@ -27,7 +27,7 @@ from . import backend
 from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, RobotSpec, WalkProgram, build_robot_spec, build_walk, fold_link_table,
                       foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
-                       _ForwardDynamicsRollout, _quat_grad_to_rot)
+                       _ForwardDynamicsRollout, _Energy, _quat_grad_to_rot)
 from .rigid_body import DifferentiableRigidBody, LinkPose, LinkVelocity
 from .urdf_utils import URDFRobotModel
 
@@ -140,6 +140,21 @@ class InverseDynamicsDerivatives(NamedTuple):
     dtau_dq: torch.Tensor               # [B, n, n] (damping never enters it)
     dtau_dqd: torch.Tensor              # [B, n, n] (with use_damping it includes diag(damping); gravity never enters it)
     dtau_dqdd: torch.Tensor             # [B, n, n] H(q), symmetric to the bit
+
+
+class EnergyDerivatives(NamedTuple):
+    """What DifferentiableRobotModel.compute_energy_derivatives returns (no autograd history on any field)."""
+    kinetic: torch.Tensor               # [B] T = 1/2 qd^T H(q) qd
+    potential: torch.Tensor             # [B] V = 9.81 sum_i m_i z_i over the bodies a joint moves
+    momentum: torch.Tensor              # [B, n] p = dT/dqd = H(q) qd
+    dkinetic_dq: torch.Tensor           # [B, n] dT/dq = C(q, qd)^T qd
+    gravity: torch.Tensor               # [B, n] dV/dq = g(q)
+
+
+class Energy(NamedTuple):
+    """What DifferentiableRobotModel.compute_energy returns: differentiable once with respect to q and qd."""
+    kinetic: torch.Tensor               # [B]
+    potential: torch.Tensor             # [B]
 
 
 class DifferentiableRobotModel(torch.nn.Module):
@@ -1752,6 +1767,77 @@ class DifferentiableRobotModel(torch.nn.Module):
             dw = self._dynamics_walk()
             return backend.lagrangian_dynamics(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), self._n_dofs,
                                                coriolis_only=coriolis_only, composed=composed)
+
+    def compute_energy_derivatives(self, q: torch.Tensor, qd: torch.Tensor, *, _composed: bool = False) -> EnergyDerivatives:
+        """The Lagrangian L = T - V and the Hamiltonian T + V of the robot at q, qd [B, n], with their first derivatives:
+            kinetic      [B]     T = 1/2 qd^T H(q) qd, summed over the bodies as 1/2 v_i . (I_i v_i) in each link's own frame (H is
+                                 never formed); >= 0, and exactly 0 where qd = 0
+            potential    [B]     V = 9.81 sum_i m_i z_i, z_i the height of body i's centre of mass above the base frame's z = 0
+                                 plane, over the bodies of regressor_links().  Links that no joint moves — the base and whatever is
+                                 fixed to it — are LEFT OUT: they add a constant to V and nothing to the other four.
+            momentum     [B, n]  p = dT/dqd = H(q) qd, the generalised momentum
+            dkinetic_dq  [B, n]  dT/dq_j = 1/2 qd^T (dH/dq_j) qd = (C^T qd)_j with compute_coriolis_matrix's C
+            gravity      [B, n]  dV/dq = compute_lagrangian_dynamics(q, qd).gravity, up to float32 rounding
+        so that Lagrange's equations read pdot = tau + dkinetic_dq - gravity and Hamilton's qdot = dHam/dp, pdot = -dHam/dq + tau
+        with dHam/dq = gravity - dkinetic_dq at fixed p.  Joint damping enters none of them.  What energy-shaping and swing-up
+        controllers, symplectic integrators, Lagrangian / Hamiltonian network losses and an energy-drift check of a rollout need.
+
+        One kernel launch (csrc/drm_energy.hip): one sweep out and one back over the tree, lighter than inverse dynamics — 56 B in
+        and 92 B out per row of a 7-DoF arm instead of the 420 B of compute_lagrangian_dynamics, two products, all-links forward
+        kinematics and a loop over the masses.  A 7-DoF arm's full 64-row tiles run a kernel that keeps everything in registers;
+        every other robot one lane per row over the ops of its walk.  With the robot's own constant-folded kernels attached this
+        entry point still runs the library kernels.  Argument handling is that of compute_lagrangian_dynamics (unbatched inputs give
+        unbatched results); works for models on the CPU and on a HIP device, with either joint model (reference_compat) and for
+        models with learnable links: their current values are used.  A row whose q or qd is not finite — or whose |q| is beyond
+        1e5, where float32 no longer resolves an angle — returns NaN in all five and changes no bit of any other row.
+
+        The results carry NO autograd history, whatever requires grad (compute_energy is the differentiable form).  (``_composed``,
+        or DRM_ENERGY_COMPOSED=1 in the environment: every row takes the general kernel, DRM_ENERGY_COMPOSED; for tests and A/B
+        measurements.)"""
+        return EnergyDerivatives(*self._compute_energy(q, qd, backend.ENERGY_OUTPUTS, bool(_composed)))
+
+    def compute_generalized_momentum(self, q: torch.Tensor, qd: torch.Tensor) -> torch.Tensor:
+        """compute_energy_derivatives(q, qd).momentum [B, n] alone, to the bit: the same launch with only p requested."""
+        return self._compute_energy(q, qd, ("momentum",), False)[2]
+
+    def compute_energy(self, q: torch.Tensor, qd: torch.Tensor) -> Energy:
+        """(kinetic [B], potential [B]) of compute_energy_derivatives, to the bit, from the same launch — and DIFFERENTIABLE with
+        respect to q and qd: one autograd node (autograd._Energy) whose forward asks the launch for all five outputs and keeps the
+        three vectors, and whose backward is
+            grad_q = gT[:, None] * dkinetic_dq + gV[:, None] * gravity,      grad_qd = gT[:, None] * momentum.
+        FIRST order only: the node is once_differentiable, a second backward through it raises.  When neither q nor qd requires
+        grad (or grad mode is off) only T and V are requested and the sweep back is not made.  No history flows to learnable link
+        parameters: their current values are used, as by compute_energy_derivatives."""
+        return Energy(*self._compute_energy_differentiable(q, qd))
+
+    @tensor_check
+    def _compute_energy(self, q, qd, want, composed):
+        assert q.ndim == 2
+        assert qd.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        assert qd.shape[1] == self._n_dofs
+        assert q.shape[0] == qd.shape[0]
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            return backend.energy(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(), self._n_dofs, want=want,
+                                  composed=composed)
+
+    @tensor_check
+    def _compute_energy_differentiable(self, q, qd):
+        assert q.ndim == 2
+        assert qd.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        assert qd.shape[1] == self._n_dofs
+        assert q.shape[0] == qd.shape[0]
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            ops_f = self._ops_f(dw).detach()
+        if torch.is_grad_enabled() and (q.requires_grad or qd.requires_grad):
+            return _Energy.apply(q, qd, dw.program, ops_f, dw.ops_i, self._n_dofs)
+        with torch.no_grad():
+            return backend.energy(dw.program, ops_f, dw.ops_i, q.detach(), qd.detach(), self._n_dofs, want=("kinetic", "potential"))[:2]
 
     def compute_inverse_dynamics_derivatives(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor,
                                              include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False, *,

@@ -210,6 +210,8 @@ extern "C" {
 #define DRM_LAGRANGIAN_COMPOSED 128 /* force the general kernel on every row (tests, A/B) */
 /* flag of drm_rnea_derivatives, beside DRM_RNEA_GRAVITY / DRM_RNEA_DAMPING */
 #define DRM_IDD_COMPOSED 256        /* force the general kernel on every row (tests, A/B) */
+/* flag of drm_energy */
+#define DRM_ENERGY_COMPOSED 512     /* force the general kernel on every row (tests, A/B) */
 
 /* error codes */
 #define DRM_OK 0
@@ -627,6 +629,40 @@ int64_t drm_rnea_derivatives_scratch_floats(const drm_walk *walk, int64_t B);
 int64_t drm_rnea_derivatives_scratch_floats_aligned(const drm_walk *walk, int64_t B);
 int drm_rnea_derivatives(const drm_walk *walk, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau,
                          float *dtau_dq, float *dtau_dqd, float *H, float *scratch, void *stream);
+
+/*
+ * The Lagrangian's own terms in one call (additive to ABI 15): the kinetic energy, the potential energy, the generalised momentum and
+ * the gradients of both energies.  What energy-shaping and swing-up control, Hamiltonian / symplectic integration (qdot = dHam/dp,
+ * pdot = -dHam/dq + tau), Lagrangian and Hamiltonian network losses and an energy-drift check of a rollout need, and what a caller
+ * otherwise composes from drm_lagrangian_dynamics (420 B per row), two products, all-links forward kinematics and the link masses.
+ *   q, qd [B, n]  ->  T [B], V [B], p [B, n], dT_dq [B, n], g [B, n]; any of the five may be NULL (not stored; with p, dT_dq and g all
+ *   NULL the sweep back is not made)
+ *   T       1/2 qd^T H(q) qd, formed as the sum over the bodies of 1/2 v_i . (I_i v_i) in each link's own frame, not via H
+ *   V       9.81 sum_i m_i z_i, z_i the height of body i's centre of mass above the base frame's z = 0 plane, over the bodies of the
+ *           walk that a joint moves.  The base and whatever is fixed to it are left out: they add a constant to V and nothing else.
+ *   p       dT/dqd = H qd:  p_j = S_j . hC_j, hC_j the spatial momentum of joint j's sub-tree in link j's frame
+ *   dT_dq   1/2 qd^T (dH/dq_j) qd = (C^T qd)_j with drm_lagrangian_dynamics' C:  -S_j . (v_j x* hC_j), no acceleration sweep
+ *   g       dV/dq: drm_lagrangian_dynamics' g up to float32 rounding
+ *   Joint damping enters none of them.
+ * One sweep out (velocity, base acceleration, height) and one back (a 6-float momentum and a 4-float mass / first moment) over the
+ * tree (csrc/drm_energy.hpp), every quantity in its link's own frame.  Serial 7-DoF arm chains (DRM_WALK_ARM_CHAIN, capacity 8), full
+ * 64-row tiles, 16-byte aligned q / qd / p / dT_dq / g and table: ONE kernel, one wavefront per tile, one row per lane, everything in
+ * registers, T and V one float per lane, the three [64, 7] tiles assembled in LDS and stored whole in 16-byte stores (56 B in, 92 B
+ * out per row).  Every other walk, the ragged tail, misaligned pointers and DRM_ENERGY_COMPOSED: one lane per row and two loops over
+ * the ops.  A walk that carries its robot's own code object runs these library kernels all the same.
+ * A row with a q or qd that is not finite, or with a |q| beyond 1e5 (float32 no longer resolves such an angle), gets NaN in every
+ * output that is written and changes no bit of any other row.
+ *   scratch   drm_energy_scratch_floats_aligned floats when q / qd / p / dT_dq / g are 16-byte aligned, drm_energy_scratch_floats floats
+ *             otherwise and with DRM_ENERGY_COMPOSED: the rows' records between the sweeps where 64 rows of them do not fit the general
+ *             kernel's LDS budget (14 n_ops + 10 n_slots floats per row and at most 2 048 tiles of 64 rows at a time; 0 for chains of
+ *             up to 9 ops: scratch may then be NULL)
+ * DRM_ERR_INVALID for a NULL q / qd, for all five outputs NULL, or a negative B; B == 0 returns DRM_OK.  Asynchronous on `stream`,
+ * never a host synchronisation, no allocation.
+ */
+int64_t drm_energy_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_energy_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_energy(const drm_walk *walk, const float *q, const float *qd, int64_t B, int32_t flags, float *T, float *V, float *p, float *dT_dq,
+               float *g, float *scratch, void *stream);
 
 /*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
