@@ -192,9 +192,14 @@ def load_library(path: str = None, kind: str = "cuda"):
         f32 = ctypes.c_float
         lib.drm_inverse_kinematics.restype = ctypes.c_int
         lib.drm_inverse_kinematics.argtypes = [wp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp, vp, i32, vp, vp, vp, vp, vp]
-        for name in ("drm_rnea_scratch_floats_aligned", "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned",
-                     "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned",
-                     "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned"):
+        for name in ("drm_rnea_scratch_floats_aligned", "drm_crba_scratch_floats_aligned",
+                     "drm_forward_dynamics_scratch_floats_aligned", "drm_forward_dynamics_rollout_scratch_floats",
+                     "drm_forward_dynamics_rollout_scratch_floats_aligned", "drm_inverse_kinematics_scratch_floats",
+                     "drm_inverse_kinematics_scratch_floats_aligned", "drm_forward_dynamics_derivatives_scratch_floats",
+                     "drm_forward_dynamics_derivatives_scratch_floats_aligned", "drm_rnea_regressor_scratch_floats",
+                     "drm_rnea_regressor_scratch_floats_aligned", "drm_lagrangian_dynamics_scratch_floats",
+                     "drm_lagrangian_dynamics_scratch_floats_aligned", "drm_rnea_derivatives_scratch_floats",
+                     "drm_rnea_derivatives_scratch_floats_aligned", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_operational_space.restype = ctypes.c_int
@@ -204,29 +209,14 @@ def load_library(path: str = None, kind: str = "cuda"):
             getattr(lib, name).argtypes = [wp, wp, i64]
         lib.drm_forward_dynamics_derivatives.restype = ctypes.c_int
         lib.drm_forward_dynamics_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-        for name in ("drm_forward_dynamics_derivatives_scratch_floats", "drm_forward_dynamics_derivatives_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64]
         lib.drm_rnea_regressor.restype = ctypes.c_int
         lib.drm_rnea_regressor.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp]
-        for name in ("drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64]
         lib.drm_lagrangian_dynamics.restype = ctypes.c_int
         lib.drm_lagrangian_dynamics.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
-        for name in ("drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64]
         lib.drm_rnea_derivatives.restype = ctypes.c_int
         lib.drm_rnea_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-        for name in ("drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64]
         lib.drm_energy.restype = ctypes.c_int
         lib.drm_energy.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
-        for name in ("drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64]
         lib.drm_special_load.restype = ctypes.c_int
         lib.drm_special_load.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.drm_fk_mse.restype = ctypes.c_int
@@ -612,6 +602,15 @@ def _rnea_scratch(lib, walk, B, device):
     return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
 
 
+def _scratch(lib, base: str, walks, B: int, composed: bool, device):
+    """The scratch of entry point ``base`` over B rows of ``walks`` (None: not needed).  The callers' tensors come from _dev_f32 /
+    _outputs / torch.empty, 16-byte aligned, so the ``_aligned`` query sizes the call; ``composed`` (the entry point's DRM_*_COMPOSED
+    flag) takes the composed path / general kernel on every row: the size for any pointers."""
+    query = getattr(lib, base + ("_scratch_floats" if composed else "_scratch_floats_aligned"))
+    need = int(query(*[ctypes.byref(w) for w in walks], B))
+    return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
+
+
 def rnea_backward(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, grad_tau, include_gravity: bool, use_damping: bool,
                   n_dofs: int, param_mask: int, want_grad_inputs: bool):
     """((grad_q, grad_qd, grad_qdd) or None, grad_ops_f [cap,32] or None) for a loss gradient on the torques."""
@@ -963,10 +962,7 @@ def inverse_kinematics(prog: WalkProgram, ops_f, ops_i, q0, target_pos, target_q
         return q, err, iters
     flags = (IK_POSITION_ONLY if target_quat is None else 0) | (IK_COMPOSED if composed else 0)
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_IK_COMPOSED takes the composed path on every row: the size for any pointers)
-    query = lib.drm_inverse_kinematics_scratch_floats if composed else lib.drm_inverse_kinematics_scratch_floats_aligned
-    need = int(query(ctypes.byref(walk), B))
-    scratch = torch.empty(need, device=q0.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_inverse_kinematics", (walk,), B, composed, q0.device)
     with _on_device(q0.device):
         _check(lib.drm_inverse_kinematics(ctypes.byref(walk), q0.data_ptr(), target_pos.data_ptr(),
                                           target_quat.data_ptr() if target_quat is not None else None, B, int(max_iters),
@@ -997,10 +993,7 @@ def operational_space(tree, chain, q, qd, include_gravity: bool, use_damping: bo
              (OSC_POSITION_ONLY if position_only else 0) | (OSC_COMPOSED if composed else 0))
     wt = _walk_struct(tree[0], tree[1].detach(), tree[2], n_dofs)
     wc = _walk_struct(chain[0], chain[1].detach(), chain[2], n_dofs)
-    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_OSC_COMPOSED takes the composed path on every row: the size for any pointers)
-    query = lib.drm_operational_space_scratch_floats if composed else lib.drm_operational_space_scratch_floats_aligned
-    need = int(query(ctypes.byref(wt), ctypes.byref(wc), B))
-    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_operational_space", (wt, wc), B, composed, q.device)
     with _on_device(q.device):
         _check(lib.drm_operational_space(ctypes.byref(wt), ctypes.byref(wc), q.data_ptr(), qd.data_ptr(), B, flags, float(reg),
                                          inertia.data_ptr(), jbar.data_ptr(), bias_acc.data_ptr(), bias_force.data_ptr(),
@@ -1026,10 +1019,7 @@ def forward_dynamics_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, f, incl
     composed = bool(composed) or os.environ.get("DRM_FDD_COMPOSED") == "1"
     flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (FDD_COMPOSED if composed else 0)
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_FDD_COMPOSED takes the composed path on every row: the size for any pointers)
-    query = lib.drm_forward_dynamics_derivatives_scratch_floats if composed else lib.drm_forward_dynamics_derivatives_scratch_floats_aligned
-    need = int(query(ctypes.byref(walk), B))
-    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_forward_dynamics_derivatives", (walk,), B, composed, q.device)
     with _on_device(q.device):
         _check(lib.drm_forward_dynamics_derivatives(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), f.data_ptr(), B, flags,
                                                     qdd.data_ptr(), dq.data_ptr(), dqd.data_ptr(), minv.data_ptr(),
@@ -1052,9 +1042,7 @@ def rnea_regressor(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity:
         return Y
     flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (REGRESSOR_COMPOSED if composed else 0)
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    query = lib.drm_rnea_regressor_scratch_floats if composed else lib.drm_rnea_regressor_scratch_floats_aligned
-    need = int(query(ctypes.byref(walk), B))
-    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_rnea_regressor", (walk,), B, composed, q.device)
     with _on_device(q.device):
         _check(lib.drm_rnea_regressor(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, Y.data_ptr(),
                                       scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
@@ -1079,10 +1067,7 @@ def lagrangian_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, cor
         return H, C, g
     composed = bool(composed) or os.environ.get("DRM_LAGRANGIAN_COMPOSED") == "1"
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_LAGRANGIAN_COMPOSED takes the general kernel on every row: the size for any pointers)
-    query = lib.drm_lagrangian_dynamics_scratch_floats if composed else lib.drm_lagrangian_dynamics_scratch_floats_aligned
-    need = int(query(ctypes.byref(walk), B))
-    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_lagrangian_dynamics", (walk,), B, composed, q.device)
     with _on_device(q.device):
         _check(lib.drm_lagrangian_dynamics(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, LAGRANGIAN_COMPOSED if composed else 0,
                                            H.data_ptr() if H is not None else None, C.data_ptr(),
@@ -1107,10 +1092,7 @@ def rnea_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravit
     composed = bool(composed) or os.environ.get("DRM_IDD_COMPOSED") == "1"
     flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (IDD_COMPOSED if composed else 0)
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_IDD_COMPOSED takes the general kernel on every row: the size for any pointers)
-    query = lib.drm_rnea_derivatives_scratch_floats if composed else lib.drm_rnea_derivatives_scratch_floats_aligned
-    need = int(query(ctypes.byref(walk), B))
-    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_rnea_derivatives", (walk,), B, composed, q.device)
     with _on_device(q.device):
         _check(lib.drm_rnea_derivatives(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, tau.data_ptr(),
                                         dq.data_ptr(), dqd.data_ptr(), H.data_ptr(),
@@ -1141,10 +1123,7 @@ def energy(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, want=ENERGY_OUTP
         return outs
     composed = bool(composed) or os.environ.get("DRM_ENERGY_COMPOSED") == "1"
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    # (_dev_f32 / _outputs / torch.empty: aligned; DRM_ENERGY_COMPOSED takes the general kernel on every row: the size for any pointers)
-    query = lib.drm_energy_scratch_floats if composed else lib.drm_energy_scratch_floats_aligned
-    need = int(query(ctypes.byref(walk), B))
-    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
+    scratch = _scratch(lib, "drm_energy", (walk,), B, composed, q.device)
     ptr = lambda t: t.data_ptr() if t is not None else None
     with _on_device(q.device):
         _check(lib.drm_energy(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, ENERGY_COMPOSED if composed else 0,

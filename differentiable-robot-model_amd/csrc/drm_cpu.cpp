@@ -31,6 +31,7 @@
 #include "drm_idd.hpp"
 #include "drm_energy.hpp"
 #include "drm_rollout.hpp"
+#include "drm_rows.hpp"
 
 namespace {
 using namespace drm_host;
@@ -55,6 +56,12 @@ int check_walk(const drm_walk *w) {
         return fail(DRM_ERR_UNSUPPORTED, "walk needs %ld save slots, the walks have %ld", w->n_slots, DRM_MAX_SLOTS);
     if (w->n_segments < 1 || w->n_segments > DRM_MAX_SEGMENTS) return fail(DRM_ERR_INVALID, "walk has %ld segments", w->n_segments);
     return DRM_OK;
+}
+
+// what the tree-sweep entry points (regressor, H / C / g, inverse-dynamics derivatives, energies) ask of a walk
+int check_sweep_walk(const drm_walk *w) {
+    if (int rc = check_walk(w)) return rc;
+    return w->n_ops < 1 ? fail(DRM_ERR_INVALID, "the walk has no ops") : DRM_OK;
 }
 
 int check_backward_walk(const drm_walk *w, uint64_t mask) {
@@ -249,11 +256,17 @@ void regressor_host_rows(const drm_walk *w, const float *q, const float *qd, con
             for (int j = 0; j < n; ++j) Yr[j * P + drm::REG_COLS * n_ops + j] = qdr[j];
     }
 }
+// one row's `count` records of N floats on this thread's heap, in the put / get shape of the rows kernels' lane view (drm_rows.hpp)
+template <int N>
+struct HostRecords : drm::Records<N, 1> {
+    std::vector<float> mem;
+    explicit HostRecords(int count) : mem((size_t)N * (count > 0 ? count : 1)) { this->base = mem.data(); }
+};
 // drm_lagrangian_dynamics, rows [b0, b0 + rows): drm_lagrangian.hpp's walk of the row, its records on this thread's heap
 void lagrangian_host_rows(const drm_walk *w, const float *q, const float *qd, int64_t b0, int64_t rows, float *H, float *C, float *g) {
     const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
     const Ctl ctl(w);
-    std::vector<float> rec((size_t)drm::LAG_REC_FLOATS * (n_ops > 0 ? n_ops : 1)), slots((size_t)drm::LAG_SLOT_FLOATS * (n_slots > 0 ? n_slots : 1));
+    HostRecords<drm::LAG_REC_FLOATS> rec(n_ops); HostRecords<drm::LAG_SLOT_FLOATS> slots(n_slots);
     const float nan = std::numeric_limits<float>::quiet_NaN();
     for (int64_t b = b0; b < b0 + rows; ++b) {
         const float *qr = q + b * n, *qdr = qd + b * n;
@@ -267,10 +280,8 @@ void lagrangian_host_rows(const drm_walk *w, const float *q, const float *qd, in
         drm::lagrangian_tree_walk(
             n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, ctl, [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
             [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
-            [&](int k, const float *x) { std::copy(x, x + drm::LAG_REC_FLOATS, rec.begin() + (size_t)drm::LAG_REC_FLOATS * k); },
-            [&](int k, float *x) { std::copy_n(rec.begin() + (size_t)drm::LAG_REC_FLOATS * k, drm::LAG_REC_FLOATS, x); },
-            [&](int s, const float *x) { std::copy(x, x + drm::LAG_SLOT_FLOATS, slots.begin() + (size_t)drm::LAG_SLOT_FLOATS * s); },
-            [&](int s, float *x) { std::copy_n(slots.begin() + (size_t)drm::LAG_SLOT_FLOATS * s, drm::LAG_SLOT_FLOATS, x); },
+            [&](int k, const float *x) { rec.put(k, x); }, [&](int k, float *x) { rec.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
             [&](int i, int j, float v) { if (Hr) Hr[i * n + j] = bad ? nan : v; },
             [&](int i, int j, float v) { if (Cr) Cr[i * n + j] = bad ? nan : v; },
             [&](int j, float v) { if (gr) gr[j] = bad ? nan : v; });
@@ -281,7 +292,7 @@ void idd_host_rows(const drm_walk *w, const float *q, const float *qd, const flo
                    float *dq, float *dqd, float *H) {
     const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
     const Ctl ctl(w);
-    std::vector<float> rec((size_t)drm::IDD_REC_FLOATS * (n_ops > 0 ? n_ops : 1)), slots((size_t)drm::IDD_SLOT_FLOATS * (n_slots > 0 ? n_slots : 1));
+    HostRecords<drm::IDD_REC_FLOATS> rec(n_ops); HostRecords<drm::IDD_SLOT_FLOATS> slots(n_slots);
     const float nan = std::numeric_limits<float>::quiet_NaN();
     for (int64_t b = b0; b < b0 + rows; ++b) {
         const float *qr = q + b * n, *qdr = qd + b * n, *qddr = qdd + b * n;
@@ -295,10 +306,8 @@ void idd_host_rows(const drm_walk *w, const float *q, const float *qd, const flo
             n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, (flags & DRM_RNEA_GRAVITY) ? 9.81f : 0.0f, (flags & DRM_RNEA_DAMPING) != 0, ctl,
             [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
             [&](int d, float &a, float &v, float &acc) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; acc = bad ? 0.0f : qddr[d]; },
-            [&](int k, const float *x) { std::copy(x, x + drm::IDD_REC_FLOATS, rec.begin() + (size_t)drm::IDD_REC_FLOATS * k); },
-            [&](int k, float *x) { std::copy_n(rec.begin() + (size_t)drm::IDD_REC_FLOATS * k, drm::IDD_REC_FLOATS, x); },
-            [&](int s, const float *x) { std::copy(x, x + drm::IDD_SLOT_FLOATS, slots.begin() + (size_t)drm::IDD_SLOT_FLOATS * s); },
-            [&](int s, float *x) { std::copy_n(slots.begin() + (size_t)drm::IDD_SLOT_FLOATS * s, drm::IDD_SLOT_FLOATS, x); },
+            [&](int k, const float *x) { rec.put(k, x); }, [&](int k, float *x) { rec.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
             [&](int which, int i, int j, float v) { if (Mr[which]) Mr[which][i * n + j] = bad ? nan : v; },
             [&](int j, float v) { if (tr) tr[j] = bad ? nan : v; });
     }
@@ -308,7 +317,7 @@ void energy_host_rows(const drm_walk *w, const float *q, const float *qd, int64_
                       float *g) {
     const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
     const Ctl ctl(w);
-    std::vector<float> rec((size_t)drm::ENERGY_REC_FLOATS * (n_ops > 0 ? n_ops : 1)), slots((size_t)drm::ENERGY_SLOT_FLOATS * (n_slots > 0 ? n_slots : 1));
+    HostRecords<drm::ENERGY_REC_FLOATS> rec(n_ops); HostRecords<drm::ENERGY_SLOT_FLOATS> slots(n_slots);
     const float nan = std::numeric_limits<float>::quiet_NaN();
     for (int64_t b = b0; b < b0 + rows; ++b) {
         const float *qr = q + b * n, *qdr = qd + b * n;
@@ -318,10 +327,8 @@ void energy_host_rows(const drm_walk *w, const float *q, const float *qd, int64_
         drm::energy_tree_walk(
             n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, p || dT || g, ctl, [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; },
             [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
-            [&](int k, const float *x) { std::copy(x, x + drm::ENERGY_REC_FLOATS, rec.begin() + (size_t)drm::ENERGY_REC_FLOATS * k); },
-            [&](int k, float *x) { std::copy_n(rec.begin() + (size_t)drm::ENERGY_REC_FLOATS * k, drm::ENERGY_REC_FLOATS, x); },
-            [&](int s, const float *x) { std::copy(x, x + drm::ENERGY_SLOT_FLOATS, slots.begin() + (size_t)drm::ENERGY_SLOT_FLOATS * s); },
-            [&](int s, float *x) { std::copy_n(slots.begin() + (size_t)drm::ENERGY_SLOT_FLOATS * s, drm::ENERGY_SLOT_FLOATS, x); },
+            [&](int k, const float *x) { rec.put(k, x); }, [&](int k, float *x) { rec.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
             [&](float Tv, float Vv) {
                 if (T) T[b] = bad ? nan : Tv;
                 if (V) V[b] = bad ? nan : Vv;
@@ -565,8 +572,7 @@ int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *, int64_t) { r
 
 int drm_rnea_regressor(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y, float *,
                        void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (int rc = check_sweep_walk(w)) return rc;
     if ((int64_t)w->n_dofs * (drm::REG_COLS * (int64_t)w->n_ops + w->n_dofs) >= (1 << 24))
         return fail(DRM_ERR_UNSUPPORTED, "a row of the regressor of this walk has 2^24 entries or more (%ld ops, %ld DoFs)", w->n_ops, w->n_dofs);
     if (!q || !qd || !Y) return fail(DRM_ERR_INVALID, "q / qd / Y must not be NULL");
@@ -582,8 +588,7 @@ int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *, int64_t
 
 int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t, float *H, float *C, float *g, float *,
                             void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (int rc = check_sweep_walk(w)) return rc;
     if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
     if (!H && !C && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
@@ -598,8 +603,7 @@ int64_t drm_rnea_derivatives_scratch_floats_aligned(const drm_walk *, int64_t) {
 
 int drm_rnea_derivatives(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau, float *dq,
                          float *dqd, float *H, float *, void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (int rc = check_sweep_walk(w)) return rc;
     if (!q || !qd || !qdd) return fail(DRM_ERR_INVALID, "q / qd / qdd must not be NULL");
     if (!tau && !dq && !dqd && !H) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
@@ -613,8 +617,7 @@ int64_t drm_energy_scratch_floats_aligned(const drm_walk *, int64_t) { return 0;
 
 int drm_energy(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t, float *T, float *V, float *p, float *dT, float *g,
                float *, void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
+    if (int rc = check_sweep_walk(w)) return rc;
     if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
     if (!T && !V && !p && !dT && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");

@@ -11,8 +11,7 @@
 //   energy_rows_kernel   every other walk (trees, hands, prismatic joints, two-op skew-axis links, fixed ops kept for learnable links),
 //                        the ragged tail of an arm launch, misaligned pointers, DRM_ENERGY_COMPOSED: one lane per row, loops over the
 //                        ops (drm_energy.hpp energy_tree_walk), ALL segments of the walk on the one wavefront.  Between the sweeps a
-//                        row keeps 14 floats per op and 10 per branch point, in LDS where 64 rows of them fit ENERGY_LDS_BYTES, else
-//                        in the caller's scratch (a persistent grid of at most ENERGY_SCRATCH_BLOCKS blocks, each with its own slice).
+//                        row keeps 14 floats per op and 10 per branch point, placed by drm_rows.hpp (LDS up to ENERGY_LDS_BYTES).
 //
 // Per row, fused, n = 7: in q, qd (56 B); out 4 (1 + 1 + 7 + 7 + 7) B = 92 B.
 #include <math.h>
@@ -20,11 +19,11 @@
 #include "drm_common.hpp"
 #include "drm_dispatch.hpp"
 #include "drm_energy.hpp"
+#include "drm_rows.hpp"
 
 namespace drm {
 
-constexpr int ENERGY_LDS_BYTES = 32 * 1024;   // per-row state of the general kernel in LDS up to here (five blocks per CU)
-constexpr int ENERGY_SCRATCH_BLOCKS = 2048;   // ... beyond: blocks of the persistent grid, each with a slice of the scratch
+constexpr int ENERGY_LDS_BYTES = 32 * 1024; // per-row state of the general kernel in LDS up to here (five blocks per CU)
 
 static inline int energy_state_floats(const drm_walk *w) { return ENERGY_REC_FLOATS * w->n_ops + ENERGY_SLOT_FLOATS * w->n_slots; }
 
@@ -90,25 +89,19 @@ __global__ void __launch_bounds__(WAVE)
     }
 }
 
-// The general kernel.  Rows [0, B) in tiles of 64, one lane per row; blocks stride over the tiles.  state: the lanes' records and
-// parked composites, [float][64 lanes] — LDS (IN_LDS) or the block's slice of the scratch.
-struct EnergyCtl {
-    const int32_t *w0, *w1;
-    __device__ void raw(int k, int &a, int &b) const { a = w0[k]; b = w1[k]; }
-    __device__ int uniform(int r) const { return __builtin_amdgcn_readfirstlane(r); }
-};
-
+// The general kernel.  Rows [0, B) in tiles of 64, one lane per row; blocks stride over the tiles.  The lanes' records and parked
+// composites: drm_rows.hpp rows_state.
 template <bool IN_LDS>
 __global__ void __launch_bounds__(WAVE)
     energy_rows_kernel(const float *__restrict__ ops_f, const int32_t *__restrict__ ops_i, int cap, int n_ops, int p_end, int n_slots, int n,
                        const float *__restrict__ q, const float *__restrict__ qd, int64_t B, int64_t n_tiles, float *__restrict__ T,
                        float *__restrict__ V, float *__restrict__ p, float *__restrict__ dT, float *__restrict__ g,
                        float *__restrict__ scratch, int state_floats) {
-    extern __shared__ __attribute__((aligned(16))) float energy_rows_lds[];
     const unsigned lane = threadIdx.x & 63u;
-    float *state = (IN_LDS ? energy_rows_lds : scratch + (int64_t)blockIdx.x * state_floats * WAVE) + lane;
-    float *recs = state, *slots = state + ENERGY_REC_FLOATS * n_ops * WAVE;
-    const EnergyCtl ctl = {ops_i + DRM_OPI_W0 * cap, ops_i + DRM_OPI_W1 * cap};
+    float *state = rows_state<IN_LDS>(scratch, state_floats);
+    const Records<ENERGY_REC_FLOATS, WAVE> recs = {state};
+    const Records<ENERGY_SLOT_FLOATS, WAVE> slots = {state + ENERGY_REC_FLOATS * n_ops * WAVE};
+    const RowsCtl ctl(ops_i, cap);
     const float nan = __builtin_nanf("");
     const bool back = p || dT || g;
     auto row = [&](int k) -> const float * { return ops_f + k * DRM_OPF_STRIDE; };
@@ -124,22 +117,8 @@ __global__ void __launch_bounds__(WAVE)
         energy_tree_walk(
             n_ops, p_end, n_slots, back, ctl, row,
             [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
-            [&](int k, const float *x) {
-#pragma unroll
-                for (int i = 0; i < ENERGY_REC_FLOATS; ++i) recs[(ENERGY_REC_FLOATS * k + i) * WAVE] = x[i];
-            },
-            [&](int k, float *x) {
-#pragma unroll
-                for (int i = 0; i < ENERGY_REC_FLOATS; ++i) x[i] = recs[(ENERGY_REC_FLOATS * k + i) * WAVE];
-            },
-            [&](int s, const float *x) {
-#pragma unroll
-                for (int i = 0; i < ENERGY_SLOT_FLOATS; ++i) slots[(ENERGY_SLOT_FLOATS * s + i) * WAVE] = x[i];
-            },
-            [&](int s, float *x) {
-#pragma unroll
-                for (int i = 0; i < ENERGY_SLOT_FLOATS; ++i) x[i] = slots[(ENERGY_SLOT_FLOATS * s + i) * WAVE];
-            },
+            [&](int k, const float *x) { recs.put(k, x); }, [&](int k, float *x) { recs.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
             [&](float Tv, float Vv) {
                 if (T) T[r] = bad ? nan : Tv;
                 if (V) V[r] = bad ? nan : Vv;
@@ -151,24 +130,6 @@ __global__ void __launch_bounds__(WAVE)
                 if (gr) gr[j] = bad ? nan : gj;
             });
     }
-}
-
-// the fused kernel takes the full tiles of what drm_lagrangian_dynamics' fused kernel takes
-static bool energy_fused(const drm_walk *w, int64_t B, bool aligned) { return arm7_walk(w) && aligned && table_aligned(w) && full_tiles_fit(B); }
-
-static int energy_check_walk(const drm_walk *w) {
-    int rc = check_walk(w);
-    if (rc) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
-    return DRM_OK;
-}
-
-// scratch of the general kernel over `rows` rows
-static int64_t energy_rows_scratch(const drm_walk *w, int64_t rows) {
-    const int64_t state = energy_state_floats(w);
-    if (rows <= 0 || state * WAVE * (int64_t)sizeof(float) <= ENERGY_LDS_BYTES) return 0;
-    const int64_t tiles = (rows + WAVE - 1) / WAVE;
-    return (tiles < ENERGY_SCRATCH_BLOCKS ? tiles : ENERGY_SCRATCH_BLOCKS) * state * WAVE;
 }
 
 template <int LINKS>
@@ -186,17 +147,15 @@ static void launch_energy_arm(const drm_walk *w, const float *q, const float *qd
 
 using namespace drm;
 
-static int64_t energy_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
-    if (energy_check_walk(w) || B <= 0) return 0;
-    const int64_t lo = energy_fused(w, B, aligned) ? B / WAVE * WAVE : 0;
-    return energy_rows_scratch(w, B - lo);
+static int64_t energy_scratch(const drm_walk *w, int64_t B, bool aligned) {
+    return rows_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, energy_state_floats(w), ENERGY_LDS_BYTES);
 }
-extern "C" int64_t drm_energy_scratch_floats(const drm_walk *w, int64_t B) { return energy_scratch_floats_impl(w, B, false); }
-extern "C" int64_t drm_energy_scratch_floats_aligned(const drm_walk *w, int64_t B) { return energy_scratch_floats_impl(w, B, true); }
+extern "C" int64_t drm_energy_scratch_floats(const drm_walk *w, int64_t B) { return energy_scratch(w, B, false); }
+extern "C" int64_t drm_energy_scratch_floats_aligned(const drm_walk *w, int64_t B) { return energy_scratch(w, B, true); }
 
 extern "C" int drm_energy(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t flags, float *T, float *V, float *p,
                           float *dT, float *g, float *scratch, void *stream) {
-    int rc = energy_check_walk(w);
+    int rc = rows_check_walk(w);
     if (rc) return rc;
     if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
     if (!T && !V && !p && !dT && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
@@ -206,7 +165,7 @@ extern "C" int drm_energy(const drm_walk *w, const float *q, const float *qd, in
     const int n = w->n_dofs;
     int64_t lo = 0;
     // (T and V are stored one float per lane: any alignment serves them)
-    if (!(flags & DRM_ENERGY_COMPOSED) && energy_fused(w, B, aligned16(q, qd, p, dT, g))) {
+    if (!(flags & DRM_ENERGY_COMPOSED) && rows_fused(w, B, aligned16(q, qd, p, dT, g))) {
         const int n_tiles = (int)(B / WAVE);
         if (arm_links(w) == 7) launch_energy_arm<7>(w, q, qd, n_tiles, T, V, p, dT, g, s);
         else launch_energy_arm<8>(w, q, qd, n_tiles, T, V, p, dT, g, s);
@@ -216,22 +175,12 @@ extern "C" int drm_energy(const drm_walk *w, const float *q, const float *qd, in
         if (lo == B) return DRM_OK;
     }
     // the general kernel over rows [lo, B)
-    const int64_t rows = B - lo, tiles = (rows + WAVE - 1) / WAVE;
-    const int state = energy_state_floats(w);
-    const size_t lds = sizeof(float) * (size_t)state * WAVE;
+    const int64_t rows = B - lo;
+    const RowsPlan plan = rows_plan(rows, energy_state_floats(w), ENERGY_LDS_BYTES);
     const int p_end = w->n_segments > 1 ? w->prefix_end : 0;
     const float *qs = q + lo * n, *qds = qd + lo * n;
     float *Ts = T ? T + lo : nullptr, *Vs = V ? V + lo : nullptr;
     float *ps = p ? p + lo * n : nullptr, *ds = dT ? dT + lo * n : nullptr, *gs = g ? g + lo * n : nullptr;
-    if (lds <= (size_t)ENERGY_LDS_BYTES) {
-        if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
-        hipLaunchKernelGGL((energy_rows_kernel<true>), dim3((unsigned)tiles), dim3(WAVE), lds, s, w->ops_f, w->ops_i, (int)w->capacity,
-                           (int)w->n_ops, p_end, (int)w->n_slots, n, qs, qds, rows, tiles, Ts, Vs, ps, ds, gs, (float *)nullptr, state);
-    } else {
-        if (!scratch) return fail(DRM_ERR_INVALID, "pass drm_energy_scratch_floats() floats of scratch");
-        const int64_t blocks = tiles < ENERGY_SCRATCH_BLOCKS ? tiles : ENERGY_SCRATCH_BLOCKS;
-        hipLaunchKernelGGL((energy_rows_kernel<false>), dim3((unsigned)blocks), dim3(WAVE), 0, s, w->ops_f, w->ops_i, (int)w->capacity,
-                           (int)w->n_ops, p_end, (int)w->n_slots, n, qs, qds, rows, tiles, Ts, Vs, ps, ds, gs, scratch, state);
-    }
-    return launched();
+    return rows_launch(energy_rows_kernel<true>, energy_rows_kernel<false>, plan, scratch, "drm_energy_scratch_floats", s, w->ops_f, w->ops_i,
+                       (int)w->capacity, (int)w->n_ops, p_end, (int)w->n_slots, n, qs, qds, rows, plan.tiles, Ts, Vs, ps, ds, gs);
 }

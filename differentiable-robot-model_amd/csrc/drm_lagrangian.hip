@@ -13,9 +13,8 @@
 //   lagrangian_rows_kernel   every other walk (trees, hands, prismatic joints, two-op skew-axis links, fixed ops kept for learnable
 //                            links), the ragged tail of an arm launch, misaligned pointers, DRM_LAGRANGIAN_COMPOSED: one lane per row,
 //                            loops over the ops (drm_lagrangian.hpp lagrangian_tree_walk), ALL segments of the walk on the one
-//                            wavefront.  Between the sweeps a row keeps twelve floats per op and 22 per branch point, in LDS where 64
-//                            rows of them fit LAG_LDS_BYTES, else in the caller's scratch (a persistent grid of at most
-//                            LAG_SCRATCH_BLOCKS blocks, each with its own slice).  Its rows of H and C are zeroed by hipMemsetAsync
+//                            wavefront.  Between the sweeps a row keeps twelve floats per op and 22 per branch point, placed by
+//                            drm_rows.hpp (LDS up to LAG_LDS_BYTES).  Its rows of H and C are zeroed by hipMemsetAsync
 //                            ahead of it and the kernel stores the entries between a joint and its ancestors only: entries between
 //                            branches are exact zeros (the regressor measured the memset against in-kernel zeros: up to 2x faster).
 //
@@ -25,11 +24,11 @@
 #include "drm_common.hpp"
 #include "drm_dispatch.hpp"
 #include "drm_lagrangian.hpp"
+#include "drm_rows.hpp"
 
 namespace drm {
 
-constexpr int LAG_LDS_BYTES = 32 * 1024;   // per-row state of the general kernel in LDS up to here (five blocks per CU)
-constexpr int LAG_SCRATCH_BLOCKS = 2048;   // ... beyond: blocks of the persistent grid, each with a slice of the scratch
+constexpr int LAG_LDS_BYTES = 32 * 1024; // per-row state of the general kernel in LDS up to here (five blocks per CU)
 
 static inline int lagrangian_state_floats(const drm_walk *w) { return LAG_REC_FLOATS * w->n_ops + LAG_SLOT_FLOATS * w->n_slots; }
 
@@ -109,25 +108,19 @@ __global__ void __launch_bounds__(WAVE)
     }
 }
 
-// The general kernel.  Rows [0, B) in tiles of 64, one lane per row; blocks stride over the tiles.  state: the lanes' records and
-// parked composites, [float][64 lanes] — LDS (IN_LDS) or the block's slice of the scratch.  H and C arrive zeroed.
-struct LagCtl {
-    const int32_t *w0, *w1;
-    __device__ void raw(int k, int &a, int &b) const { a = w0[k]; b = w1[k]; }
-    __device__ int uniform(int r) const { return __builtin_amdgcn_readfirstlane(r); }
-};
-
+// The general kernel.  Rows [0, B) in tiles of 64, one lane per row; blocks stride over the tiles.  The lanes' records and parked
+// composites: drm_rows.hpp rows_state.  H and C arrive zeroed.
 template <bool IN_LDS>
 __global__ void __launch_bounds__(WAVE)
     lagrangian_rows_kernel(const float *__restrict__ ops_f, const int32_t *__restrict__ ops_i, int cap, int n_ops, int p_end, int n_slots,
                            int n, const float *__restrict__ q, const float *__restrict__ qd, int64_t B, int64_t n_tiles,
                            float *__restrict__ H, float *__restrict__ C, float *__restrict__ g, float *__restrict__ scratch,
                            int state_floats) {
-    extern __shared__ __attribute__((aligned(16))) float lag_rows_lds[];
     const unsigned lane = threadIdx.x & 63u;
-    float *state = (IN_LDS ? lag_rows_lds : scratch + (int64_t)blockIdx.x * state_floats * WAVE) + lane;
-    float *recs = state, *slots = state + LAG_REC_FLOATS * n_ops * WAVE;
-    const LagCtl ctl = {ops_i + DRM_OPI_W0 * cap, ops_i + DRM_OPI_W1 * cap};
+    float *state = rows_state<IN_LDS>(scratch, state_floats);
+    const Records<LAG_REC_FLOATS, WAVE> recs = {state};
+    const Records<LAG_SLOT_FLOATS, WAVE> slots = {state + LAG_REC_FLOATS * n_ops * WAVE};
+    const RowsCtl ctl(ops_i, cap);
     const float nan = __builtin_nanf("");
     auto row = [&](int k) -> const float * { return ops_f + k * DRM_OPF_STRIDE; };
 #pragma unroll 1
@@ -142,22 +135,8 @@ __global__ void __launch_bounds__(WAVE)
         lagrangian_tree_walk(
             n_ops, p_end, n_slots, ctl, row,
             [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
-            [&](int k, const float *x) {
-#pragma unroll
-                for (int i = 0; i < LAG_REC_FLOATS; ++i) recs[(LAG_REC_FLOATS * k + i) * WAVE] = x[i];
-            },
-            [&](int k, float *x) {
-#pragma unroll
-                for (int i = 0; i < LAG_REC_FLOATS; ++i) x[i] = recs[(LAG_REC_FLOATS * k + i) * WAVE];
-            },
-            [&](int s, const float *x) {
-#pragma unroll
-                for (int i = 0; i < LAG_SLOT_FLOATS; ++i) slots[(LAG_SLOT_FLOATS * s + i) * WAVE] = x[i];
-            },
-            [&](int s, float *x) {
-#pragma unroll
-                for (int i = 0; i < LAG_SLOT_FLOATS; ++i) x[i] = slots[(LAG_SLOT_FLOATS * s + i) * WAVE];
-            },
+            [&](int k, const float *x) { recs.put(k, x); }, [&](int k, float *x) { recs.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
             [&](int i, int j, float v) {
                 if (Hr && i < n && j < n) Hr[i * n + j] = bad ? nan : v;
             },
@@ -168,26 +147,6 @@ __global__ void __launch_bounds__(WAVE)
                 if (gr && j < n) gr[j] = bad ? nan : v;
             });
     }
-}
-
-// the fused kernel takes the full tiles of what drm_forward_dynamics_derivatives' fused kernel takes
-static bool lagrangian_fused(const drm_walk *w, int64_t B, bool aligned) {
-    return arm7_walk(w) && aligned && table_aligned(w) && full_tiles_fit(B);
-}
-
-static int lagrangian_check_walk(const drm_walk *w) {
-    int rc = check_walk(w);
-    if (rc) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
-    return DRM_OK;
-}
-
-// scratch of the general kernel over `rows` rows
-static int64_t lagrangian_rows_scratch(const drm_walk *w, int64_t rows) {
-    const int64_t state = lagrangian_state_floats(w);
-    if (rows <= 0 || state * WAVE * (int64_t)sizeof(float) <= LAG_LDS_BYTES) return 0;
-    const int64_t tiles = (rows + WAVE - 1) / WAVE;
-    return (tiles < LAG_SCRATCH_BLOCKS ? tiles : LAG_SCRATCH_BLOCKS) * state * WAVE;
 }
 
 template <int LINKS>
@@ -205,19 +164,15 @@ static void launch_lagrangian_arm(const drm_walk *w, const float *q, const float
 
 using namespace drm;
 
-static int64_t lagrangian_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
-    if (lagrangian_check_walk(w) || B <= 0) return 0;
-    const int64_t lo = lagrangian_fused(w, B, aligned) ? B / WAVE * WAVE : 0;
-    return lagrangian_rows_scratch(w, B - lo);
+static int64_t lagrangian_scratch(const drm_walk *w, int64_t B, bool aligned) {
+    return rows_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, lagrangian_state_floats(w), LAG_LDS_BYTES);
 }
-extern "C" int64_t drm_lagrangian_dynamics_scratch_floats(const drm_walk *w, int64_t B) { return lagrangian_scratch_floats_impl(w, B, false); }
-extern "C" int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *w, int64_t B) {
-    return lagrangian_scratch_floats_impl(w, B, true);
-}
+extern "C" int64_t drm_lagrangian_dynamics_scratch_floats(const drm_walk *w, int64_t B) { return lagrangian_scratch(w, B, false); }
+extern "C" int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *w, int64_t B) { return lagrangian_scratch(w, B, true); }
 
 extern "C" int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t flags, float *H, float *C,
                                        float *g, float *scratch, void *stream) {
-    int rc = lagrangian_check_walk(w);
+    int rc = rows_check_walk(w);
     if (rc) return rc;
     if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
     if (!H && !C && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
@@ -226,7 +181,7 @@ extern "C" int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const 
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;
     int64_t lo = 0;
-    if (!(flags & DRM_LAGRANGIAN_COMPOSED) && lagrangian_fused(w, B, aligned16(q, qd, H, C, g))) {
+    if (!(flags & DRM_LAGRANGIAN_COMPOSED) && rows_fused(w, B, aligned16(q, qd, H, C, g))) {
         const int n_tiles = (int)(B / WAVE);
         if (arm_links(w) == 7) launch_lagrangian_arm<7>(w, q, qd, n_tiles, H, C, g, s);
         else launch_lagrangian_arm<8>(w, q, qd, n_tiles, H, C, g, s);
@@ -236,26 +191,13 @@ extern "C" int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const 
         if (lo == B) return DRM_OK;
     }
     // the general kernel over rows [lo, B)
-    const int64_t rows = B - lo, tiles = (rows + WAVE - 1) / WAVE;
-    const int state = lagrangian_state_floats(w);
-    const size_t lds = sizeof(float) * (size_t)state * WAVE;
+    const int64_t rows = B - lo;
+    const RowsPlan plan = rows_plan(rows, lagrangian_state_floats(w), LAG_LDS_BYTES);
     const int p_end = w->n_segments > 1 ? w->prefix_end : 0;
     const float *qs = q + lo * n, *qds = qd + lo * n;
     float *Hs = H ? H + lo * n * n : nullptr, *Cs = C ? C + lo * n * n : nullptr, *gs = g ? g + lo * n : nullptr;
-    for (float *M : {Hs, Cs}) {
-        if (!M) continue;
-        const hipError_t e = hipMemsetAsync(M, 0, sizeof(float) * (size_t)rows * n * n, s);
-        if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
-    }
-    if (lds <= (size_t)LAG_LDS_BYTES) {
-        if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
-        hipLaunchKernelGGL((lagrangian_rows_kernel<true>), dim3((unsigned)tiles), dim3(WAVE), lds, s, w->ops_f, w->ops_i, (int)w->capacity,
-                           (int)w->n_ops, p_end, (int)w->n_slots, n, qs, qds, rows, tiles, Hs, Cs, gs, (float *)nullptr, state);
-    } else {
-        if (!scratch) return fail(DRM_ERR_INVALID, "pass drm_lagrangian_dynamics_scratch_floats() floats of scratch");
-        const int64_t blocks = tiles < LAG_SCRATCH_BLOCKS ? tiles : LAG_SCRATCH_BLOCKS;
-        hipLaunchKernelGGL((lagrangian_rows_kernel<false>), dim3((unsigned)blocks), dim3(WAVE), 0, s, w->ops_f, w->ops_i, (int)w->capacity,
-                           (int)w->n_ops, p_end, (int)w->n_slots, n, qs, qds, rows, tiles, Hs, Cs, gs, scratch, state);
-    }
-    return launched();
+    rc = rows_zero({Hs, Cs}, (size_t)rows * n * n, s);
+    if (rc) return rc;
+    return rows_launch(lagrangian_rows_kernel<true>, lagrangian_rows_kernel<false>, plan, scratch, "drm_lagrangian_dynamics_scratch_floats", s,
+                       w->ops_f, w->ops_i, (int)w->capacity, (int)w->n_ops, p_end, (int)w->n_slots, n, qs, qds, rows, plan.tiles, Hs, Cs, gs);
 }

@@ -17,8 +17,7 @@
 //                           an arm launch, misaligned pointers, DRM_REGRESSOR_COMPOSED: one lane per row, a loop over the ops
 //                           (drm_regressor.hpp regressor_tree_walk), ALL segments of the walk on the one wavefront.  Between ops a
 //                           row keeps cos / sin / value of every joint and the motions of the open branch points: 3 n_ops +
-//                           12 n_slots floats, in LDS where 64 rows of them fit REG_LDS_BYTES, else in the caller's scratch (a
-//                           persistent grid of at most REG_SCRATCH_BLOCKS blocks, each with its own slice).  Its rows of Y are
+//                           12 n_slots floats, placed by drm_rows.hpp (LDS up to REG_LDS_BYTES).  Its rows of Y are
 //                           zeroed by ONE hipMemsetAsync ahead of it and the kernel stores the rows of a body's ancestors only: on a
 //                           tree most of Y is structural zeros (Allegro: 4 of 16 joints above a body), and lanes writing them ten
 //                           floats at a time took twice as long (573 against 287 us, 65 536 Allegro rows; Fetch 432 against 283).
@@ -29,12 +28,12 @@
 #include "drm_common.hpp"
 #include "drm_dispatch.hpp"
 #include "drm_regressor.hpp"
+#include "drm_rows.hpp"
 
 namespace drm {
 
-constexpr int REG_LDS_BYTES = 20 * 1024;   // per-row state of the general kernel in LDS up to here (eight blocks per CU)
-constexpr int REG_SCRATCH_BLOCKS = 2048;   // ... beyond: blocks of the persistent grid, each with a slice of the scratch
-constexpr int REG_ARM_WAVES = 4;           // wavefronts of the fused kernel's block: they share the bodies of a tile
+constexpr int REG_LDS_BYTES = 20 * 1024; // per-row state of the general kernel in LDS up to here (eight blocks per CU)
+constexpr int REG_ARM_WAVES = 4;         // wavefronts of the fused kernel's block: they share the bodies of a tile
 
 static inline int regressor_state_floats(const drm_walk *w) { return 3 * w->n_ops + 12 * w->n_slots; }
 
@@ -107,28 +106,21 @@ __global__ void __launch_bounds__(REG_ARM_WAVES *WAVE)
     for (int i = (int)threadIdx.x; i < 16 * RP; i += REG_ARM_WAVES * WAVE) g4[i] = l4[i];
 }
 
-// The general kernel.  Rows [0, B) in tiles of 64, one lane per row; blocks stride over the tiles.  state: the lanes' records,
-// [record float][64 lanes] — LDS (IN_LDS) or the block's slice of the scratch.  Y arrives zeroed: only the ancestors' rows are stored.
-struct RegCtl {
-    const int32_t *w0, *w1;
-    __device__ void raw(int k, int &a, int &b) const { a = w0[k]; b = w1[k]; }
-    __device__ int uniform(int r) const { return __builtin_amdgcn_readfirstlane(r); }
-};
-
+// The general kernel.  Rows [0, B) in tiles of 64, one lane per row; blocks stride over the tiles.  The lanes' records, [record
+// float][64 lanes]: drm_rows.hpp rows_state.  Y arrives zeroed: only the ancestors' rows are stored.
 template <bool IN_LDS>
 __global__ void __launch_bounds__(WAVE)
     regressor_rows_kernel(const float *__restrict__ ops_f, const int32_t *__restrict__ ops_i, int cap, int n_ops, int p_end, int n,
                           const float *__restrict__ q, const float *__restrict__ qd, const float *__restrict__ qdd, int64_t B,
                           int64_t n_tiles, int flags, float *__restrict__ Y, float *__restrict__ scratch, int state_floats) {
-    extern __shared__ __attribute__((aligned(16))) float reg_rows_lds[];
     const unsigned lane = threadIdx.x & 63u;
-    float *state = (IN_LDS ? reg_rows_lds : scratch + (int64_t)blockIdx.x * state_floats * WAVE) + lane;
+    float *state = rows_state<IN_LDS>(scratch, state_floats);
     float *trig = state, *slots = state + 3 * n_ops * WAVE;
     const int n_slots = (state_floats - 3 * n_ops) / 12;
     const bool damping = flags & DRM_RNEA_DAMPING;
     const float g = (flags & DRM_RNEA_GRAVITY) ? 9.81f : 0.0f;
     const int P = REG_COLS * n_ops + (damping ? n : 0);
-    const RegCtl ctl = {ops_i + DRM_OPI_W0 * cap, ops_i + DRM_OPI_W1 * cap};
+    const RowsCtl ctl(ops_i, cap);
     auto row = [&](int k) -> const float * { return ops_f + k * DRM_OPF_STRIDE; };
 #pragma unroll 1
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -166,15 +158,9 @@ __global__ void __launch_bounds__(WAVE)
     }
 }
 
-// the fused kernel takes the full tiles of what drm_forward_dynamics_derivatives' fused kernel takes
-static bool regressor_fused(const drm_walk *w, int64_t B, bool aligned) {
-    return arm7_walk(w) && aligned && table_aligned(w) && full_tiles_fit(B);
-}
-
 static int regressor_check_walk(const drm_walk *w) {
-    int rc = check_walk(w);
+    int rc = rows_check_walk(w);
     if (rc) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
     // the largest table: a row of Y is addressed with 32-bit offsets inside the kernels
     if ((int64_t)w->n_dofs * (REG_COLS * (int64_t)w->n_ops + w->n_dofs) >= (1 << 24))
         return fail(DRM_ERR_UNSUPPORTED, "a row of the regressor of this walk has 2^24 entries or more (%s%ld ops, %ld DoFs)", "", (long)w->n_ops,
@@ -182,26 +168,16 @@ static int regressor_check_walk(const drm_walk *w) {
     return DRM_OK;
 }
 
-// scratch of the general kernel over `rows` rows
-static int64_t regressor_rows_scratch(const drm_walk *w, int64_t rows) {
-    const int64_t state = regressor_state_floats(w);
-    if (rows <= 0 || state * WAVE * (int64_t)sizeof(float) <= REG_LDS_BYTES) return 0;
-    const int64_t tiles = (rows + WAVE - 1) / WAVE;
-    return (tiles < REG_SCRATCH_BLOCKS ? tiles : REG_SCRATCH_BLOCKS) * state * WAVE;
-}
-
 } // namespace drm
 
 using namespace drm;
 
-static int64_t regressor_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
-    if (regressor_check_walk(w) || B <= 0) return 0;
-    const int64_t lo = regressor_fused(w, B, aligned) ? B / WAVE * WAVE : 0;
-    // (DRM_REGRESSOR_COMPOSED sends an arm's rows through the general kernel: its state fits LDS, no scratch either way)
-    return regressor_rows_scratch(w, B - lo);
+// (DRM_REGRESSOR_COMPOSED sends an arm's rows through the general kernel: its state fits LDS, no scratch either way)
+static int64_t regressor_scratch(const drm_walk *w, int64_t B, bool aligned) {
+    return regressor_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, regressor_state_floats(w), REG_LDS_BYTES);
 }
-extern "C" int64_t drm_rnea_regressor_scratch_floats(const drm_walk *w, int64_t B) { return regressor_scratch_floats_impl(w, B, false); }
-extern "C" int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *w, int64_t B) { return regressor_scratch_floats_impl(w, B, true); }
+extern "C" int64_t drm_rnea_regressor_scratch_floats(const drm_walk *w, int64_t B) { return regressor_scratch(w, B, false); }
+extern "C" int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *w, int64_t B) { return regressor_scratch(w, B, true); }
 
 extern "C" int drm_rnea_regressor(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y,
                                   float *scratch, void *stream) {
@@ -215,7 +191,7 @@ extern "C" int drm_rnea_regressor(const drm_walk *w, const float *q, const float
     const int kflags = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
     const int64_t P = (int64_t)REG_COLS * w->n_ops + ((flags & DRM_RNEA_DAMPING) ? n : 0);
     int64_t lo = 0;
-    if (!(flags & DRM_REGRESSOR_COMPOSED) && regressor_fused(w, B, aligned16(q, qd, qdd, Y))) {
+    if (!(flags & DRM_REGRESSOR_COMPOSED) && rows_fused(w, B, aligned16(q, qd, qdd, Y))) {
         const int n_tiles = (int)(B / WAVE);
         const size_t lds = sizeof(float) * (size_t)(8 * DRM_OPF_STRIDE + WAVE * n * P);
         if (arm_links(w) == 7) {
@@ -235,23 +211,13 @@ extern "C" int drm_rnea_regressor(const drm_walk *w, const float *q, const float
         if (lo == B) return DRM_OK;
     }
     // the general kernel over rows [lo, B)
-    const int64_t rows = B - lo, tiles = (rows + WAVE - 1) / WAVE;
-    const int state = regressor_state_floats(w);
-    const size_t lds = sizeof(float) * (size_t)state * WAVE;
+    const int64_t rows = B - lo;
+    const RowsPlan plan = rows_plan(rows, regressor_state_floats(w), REG_LDS_BYTES);
     const int p_end = w->n_segments > 1 ? w->prefix_end : 0;
     const float *qs = q + lo * n, *qds = qd + lo * n, *qdds = qdd ? qdd + lo * n : nullptr;
     float *Ys = Y + lo * n * P;
-    const hipError_t e = hipMemsetAsync(Ys, 0, sizeof(float) * (size_t)rows * n * P, s);
-    if (e != hipSuccess) return fail(DRM_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
-    if (lds <= (size_t)REG_LDS_BYTES) {
-        if (!grid_fits(tiles)) return fail(DRM_ERR_UNSUPPORTED, "batch too large");
-        hipLaunchKernelGGL((regressor_rows_kernel<true>), dim3((unsigned)tiles), dim3(WAVE), lds, s, w->ops_f, w->ops_i, (int)w->capacity,
-                           (int)w->n_ops, p_end, n, qs, qds, qdds, rows, tiles, kflags, Ys, (float *)nullptr, state);
-    } else {
-        if (!scratch) return fail(DRM_ERR_INVALID, "pass drm_rnea_regressor_scratch_floats() floats of scratch");
-        const int64_t blocks = tiles < REG_SCRATCH_BLOCKS ? tiles : REG_SCRATCH_BLOCKS;
-        hipLaunchKernelGGL((regressor_rows_kernel<false>), dim3((unsigned)blocks), dim3(WAVE), 0, s, w->ops_f, w->ops_i, (int)w->capacity,
-                           (int)w->n_ops, p_end, n, qs, qds, qdds, rows, tiles, kflags, Ys, scratch, state);
-    }
-    return launched();
+    rc = rows_zero({Ys}, (size_t)rows * n * P, s);
+    if (rc) return rc;
+    return rows_launch(regressor_rows_kernel<true>, regressor_rows_kernel<false>, plan, scratch, "drm_rnea_regressor_scratch_floats", s, w->ops_f,
+                       w->ops_i, (int)w->capacity, (int)w->n_ops, p_end, n, qs, qds, qdds, rows, plan.tiles, kflags, Ys);
 }

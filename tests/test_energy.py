@@ -563,6 +563,12 @@ def test_gpu_long_chain_keeps_its_records_in_the_scratch(tmp_path):
 
 
 @pytest.mark.gpu
+def test_gpu_persistent_grid_beyond_2048_tiles(tmp_path):
+    from test_lagrangian import persistent_grid_check
+    persistent_grid_check(tmp_path, "drm_energy_scratch_floats_aligned", lambda m, q, qd: m.compute_energy_derivatives(q, qd))
+
+
+@pytest.mark.gpu
 def test_gpu_interface():
     interface_check("cuda:0")
 

@@ -297,6 +297,37 @@ def test_scratch_queries_answer_zero_without_a_device():
         assert lib.drm_last_error() != b""
 
 
+# entry point: (floats a row keeps per op, per save slot, bytes of LDS up to which 64 rows of them stay out of the scratch)
+ROWS_KERNEL_STATE = {"drm_rnea_regressor": (3, 12, 20 * 1024), "drm_lagrangian_dynamics": (12, 22, 32 * 1024),
+                     "drm_rnea_derivatives": (15, 28, 32 * 1024), "drm_energy": (14, 10, 32 * 1024)}
+
+
+def test_scratch_of_the_tree_sweep_entry_points(tmp_path):
+    """The scratch queries of the regressor, H / C / g, the inverse-dynamics derivatives and the energies are host arithmetic (no
+    device needed): nothing while 64 rows of state fit the entry point's LDS limit, else one slice of 64 rows of state per block of
+    a persistent grid of at most 2048 blocks.  A 7-DoF arm's full tiles go to the fused kernel when the caller's pointers are
+    aligned (the ``_aligned`` query): only the ragged tail is left."""
+    from helpers import load_model
+    from test_lagrangian import walk_of
+    from test_max_sizes import chain_model
+    lib = backend.load_library()
+    models = {name: load_model(name) for name in ("panda_no_gripper", "allegro_left", "iiwa7_allegro")}
+    models["chain30"] = chain_model(tmp_path, 30)
+    needs_scratch = {"panda_no_gripper": (), "allegro_left": ("drm_lagrangian_dynamics", "drm_rnea_derivatives", "drm_energy"),
+                     "iiwa7_allegro": tuple(ROWS_KERNEL_STATE), "chain30": tuple(ROWS_KERNEL_STATE)}
+    for robot, model in models.items():
+        walk, arm = walk_of(model), robot == "panda_no_gripper"
+        for base, (rec, slot, limit) in ROWS_KERNEL_STATE.items():
+            state = rec * walk.n_ops + slot * walk.n_slots
+            assert (256 * state > limit) == (base in needs_scratch[robot]), (robot, base, state)
+            for suffix in ("_scratch_floats", "_scratch_floats_aligned"):
+                for B in (0, 1, 64, 65, 64 * 2048, 64 * 2048 + 1):
+                    rows = B % 64 if arm and B >= 64 and suffix.endswith("_aligned") else B
+                    want = 0 if 256 * state <= limit else min((rows + 63) // 64, 2048) * state * 64
+                    got = int(getattr(lib, base + suffix)(ctypes.byref(walk), ctypes.c_int64(B)))
+                    assert got == want, (robot, base + suffix, B, got, want)
+
+
 @pytest.mark.gpu
 def test_gpu_scratch_of_the_persistent_kernels():
     """Robots with a long segment (an arm carrying a hand) need caller-owned scratch wherever their rows go through the loop

@@ -523,6 +523,33 @@ def test_gpu_long_chain_keeps_its_records_in_the_scratch(tmp_path):
     assert backend.load_library().drm_lagrangian_dynamics_scratch_floats(ctypes.byref(walk_of(model)), 65) > 0
 
 
+def persistent_grid_check(tmp_path, query, compute):
+    """test_max_sizes.chain_model's 11-joint chain is the shortest whose 64 rows of records leave a 32 KB LDS limit for the scratch,
+    and 64 * 2048 + 65 rows are more tiles than the persistent grid has blocks: blocks 0 and 1 walk a second tile through the slice of
+    the scratch they used for their first, and the last tile is ragged.  The scratch does not grow past 2048 tiles.  Rows share
+    nothing, so the rows of the one big call equal the same rows computed 65 at a time to the bit: the first 65, the 65 from row
+    64 * 2048 on, and the last 65 (which here are the same rows).  Truth at 65 rows: the long-chain tests."""
+    from differentiable_robot_model_amd import backend
+    from helpers import sample_states
+    from test_max_sizes import chain_model
+    model = chain_model(tmp_path, 11, "cuda")
+    full, B = 64 * 2048, 64 * 2048 + 65
+    fn, walk = getattr(backend.load_library(), query), walk_of(model)
+    need = int(fn(ctypes.byref(walk), B))
+    assert need > 0 and need == int(fn(ctypes.byref(walk), full))
+    q, qd, _ = (torch.from_numpy(x).cuda() for x in sample_states(model, B, seed=0))
+    big = compute(model, q, qd)
+    for lo in (0, full, B - 65):
+        part = compute(model, q[lo:lo + 65].clone(), qd[lo:lo + 65].clone())
+        for name, whole, rows in zip(big._fields, big, part):
+            assert rows.shape[0] == 65 and torch.equal(whole[lo:lo + 65], rows), (name, lo)
+
+
+@pytest.mark.gpu
+def test_gpu_persistent_grid_beyond_2048_tiles(tmp_path):
+    persistent_grid_check(tmp_path, "drm_lagrangian_dynamics_scratch_floats_aligned", lambda m, q, qd: m.compute_lagrangian_dynamics(q, qd))
+
+
 @pytest.mark.gpu
 def test_gpu_interface():
     interface_check("cuda:0")
