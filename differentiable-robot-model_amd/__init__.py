@@ -18,6 +18,7 @@ from .robot_model import (  # noqa: F401
     InverseDynamicsDerivatives,
     EnergyDerivatives,
     Energy,
+    LinkMotion,
 )
 
 __version__ = "0.1.0"

@@ -10,6 +10,7 @@ here one node per public method:
     _MassMatrix       compute_lagrangian_inertia_matrix                               drm_crba / drm_rnea_backward per column
     _ForwardDynamics  compute_forward_dynamics (implicit differentiation)             drm_forward_dynamics / drm_rnea_backward
     _Energy           compute_energy (T, V and their gradients from ONE launch; first order only)          drm_energy
+    _LinkAdjoint      compute_link_velocities / compute_external_torques (each the other's backward)       drm_link_motion, drm_external_torques
     _FirstOrderOnly   marks the gradients of _FkMse computed under create_graph=True (differentiating through them raises)
     _GradLaunch       a first-order gradient launch as a differentiable node (create_graph=True: second derivatives with respect to
                       q / qd / qdd / f, the output cotangents and — round 6 — the walk's table, i.e. the learnable link parameters)
@@ -724,3 +725,43 @@ class _Energy(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             grad_qd = (gT[:, None] * p).to(ctx.dtypes[1])
         return grad_q, grad_qd, None, None, None, None
+
+
+class _LinkAdjoint(torch.autograd.Function):
+    """The two adjoint sweeps over a many-target FK walk (backend.link_motion, backend.external_torques, csrc/drm_links.hip) as ONE
+    node, in either direction.  With J the stacked link Jacobians [lin_jac_t; ang_jac_t] at q:
+        torques=False   (lin_vel, ang_vel) [B, T, 3] = J qd            backward: grad_qd = J^T (g_lin, g_ang) — the torques launch
+        torques=True    tau [B, n] = J^T (force, torque)               backward: (grad_force, grad_torque) = J g_tau — the motion launch
+    so each gradient IS the other method's forward on the same arguments, to the bit.  First order only (once_differentiable): a second
+    backward through it raises.  No gradient with respect to q (it needs the kinematic Hessian): the callers refuse a q that requires
+    grad.  The walk's table is a constant of the node: no history flows to learnable link parameters."""
+
+    @staticmethod
+    def forward(ctx, torques, q, a, b, prog, ops_f, ops_i, n_targets, n_dofs, composed):
+        q = q.detach()
+        ctx.save_for_backward(q)
+        ctx.call = (prog, ops_f, ops_i, n_targets, n_dofs, composed)
+        ctx.torques = torques
+        ctx.dtypes = (a.dtype if a is not None else None, b.dtype if b is not None else None)
+        if torques:
+            return backend.external_torques(prog, ops_f, ops_i, q, a.detach() if a is not None else None,
+                                            b.detach() if b is not None else None, n_targets, n_dofs, composed=composed)
+        out = backend.link_motion(prog, ops_f, ops_i, q, a.detach(), None, n_targets, n_dofs, want=("linear_velocity", "angular_velocity"),
+                                  composed=composed)
+        return out[1], out[2]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        (q,) = ctx.saved_tensors
+        prog, ops_f, ops_i, n_targets, n_dofs, composed = ctx.call
+        ga = gb = None
+        if ctx.torques:
+            want = tuple(name for name, need in zip(("linear_velocity", "angular_velocity"), ctx.needs_input_grad[2:4]) if need)
+            if want:
+                out = backend.link_motion(prog, ops_f, ops_i, q, grads[0], None, n_targets, n_dofs, want=want, composed=composed)
+                ga = out[1].to(ctx.dtypes[0]) if out[1] is not None else None
+                gb = out[2].to(ctx.dtypes[1]) if out[2] is not None else None
+        elif ctx.needs_input_grad[2]:
+            ga = backend.external_torques(prog, ops_f, ops_i, q, grads[0], grads[1], n_targets, n_dofs, composed=composed).to(ctx.dtypes[0])
+        return None, None, ga, gb, None, None, None, None, None, None

@@ -32,6 +32,7 @@ REGRESSOR_COMPOSED = 64       # include/drm_hip.h DRM_REGRESSOR_COMPOSED
 LAGRANGIAN_COMPOSED = 128     # include/drm_hip.h DRM_LAGRANGIAN_COMPOSED
 IDD_COMPOSED = 256            # include/drm_hip.h DRM_IDD_COMPOSED
 ENERGY_COMPOSED = 512         # include/drm_hip.h DRM_ENERGY_COMPOSED
+LINKS_COMPOSED = 1024         # include/drm_hip.h DRM_LINKS_COMPOSED
 REGRESSOR_COLS = 10           # columns per body: m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
@@ -99,7 +100,9 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned",
            "drm_lagrangian_dynamics", "drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned",
            "drm_rnea_derivatives", "drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned",
-           "drm_energy", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned")
+           "drm_energy", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
+           "drm_link_motion", "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
+           "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -199,7 +202,9 @@ def load_library(path: str = None, kind: str = "cuda"):
                      "drm_forward_dynamics_derivatives_scratch_floats_aligned", "drm_rnea_regressor_scratch_floats",
                      "drm_rnea_regressor_scratch_floats_aligned", "drm_lagrangian_dynamics_scratch_floats",
                      "drm_lagrangian_dynamics_scratch_floats_aligned", "drm_rnea_derivatives_scratch_floats",
-                     "drm_rnea_derivatives_scratch_floats_aligned", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned"):
+                     "drm_rnea_derivatives_scratch_floats_aligned", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
+                     "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
+                     "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         lib.drm_operational_space.restype = ctypes.c_int
@@ -217,6 +222,10 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_rnea_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
         lib.drm_energy.restype = ctypes.c_int
         lib.drm_energy.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+        lib.drm_link_motion.restype = ctypes.c_int
+        lib.drm_link_motion.argtypes = [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        lib.drm_external_torques.restype = ctypes.c_int
+        lib.drm_external_torques.argtypes = [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
         lib.drm_special_load.restype = ctypes.c_int
         lib.drm_special_load.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.drm_fk_mse.restype = ctypes.c_int
@@ -1129,6 +1138,72 @@ def energy(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, want=ENERGY_OUTP
         _check(lib.drm_energy(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, ENERGY_COMPOSED if composed else 0,
                               *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
     return outs
+
+
+LINK_MOTION_OUTPUTS = ("position", "linear_velocity", "angular_velocity", "linear_acceleration", "angular_acceleration")
+
+
+def _links_composed(composed) -> bool:
+    return bool(composed) or os.environ.get("DRM_LINKS_COMPOSED") == "1"
+
+
+def link_motion(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, n_targets: int, n_dofs: int, want=LINK_MOTION_OUTPUTS, composed: bool = False):
+    """(pos, lin_vel, ang_vel, lin_acc, ang_acc), each [B, T, 3] in world axes at the link origins, of the T targets of a many-target
+    FK walk in one launch (include/drm_hip.h drm_link_motion).  ``qd`` / ``qdd`` None: zero.  ``want`` names the outputs to compute
+    (LINK_MOTION_OUTPUTS); the others come back as None, neither stored nor, where that saves work, formed.  ``composed`` (or
+    DRM_LINKS_COMPOSED=1 in the environment) forces the general kernel on every row (tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    q = _dev_f32(q, "q", n_dofs)
+    qd = _dev_f32(qd, "qd", n_dofs) if qd is not None else None
+    qdd = _dev_f32(qdd, "qdd", n_dofs) if qdd is not None else None
+    B = int(q.shape[0])
+    if any(t is not None and t.shape[0] != B for t in (qd, qdd)):
+        raise ValueError("q / qd / qdd batch sizes differ")
+    want = tuple(want)
+    if not want or any(w not in LINK_MOTION_OUTPUTS for w in want):
+        raise ValueError("want must name at least one of %s" % (LINK_MOTION_OUTPUTS,))
+    made = dict(zip(want, _outputs(q.device, *[(B, n_targets, 3)] * len(want))))
+    outs = tuple(made.get(name) for name in LINK_MOTION_OUTPUTS)
+    if B == 0:
+        return outs
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _scratch(lib, "drm_link_motion", (walk,), B, composed, q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_link_motion(ctypes.byref(walk), q.data_ptr(), ptr(qd), ptr(qdd), B, n_targets, LINKS_COMPOSED if composed else 0,
+                                   *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
+    return outs
+
+
+def external_torques(prog: WalkProgram, ops_f, ops_i, q, force, torque, n_targets: int, n_dofs: int, composed: bool = False):
+    """tau [B, n] = sum_t lin_jac_t^T force[:, t] + ang_jac_t^T torque[:, t] of wrenches [B, T, 3] on the T targets of a many-target
+    FK walk, acting at the link origins in world axes, in one launch (include/drm_hip.h drm_external_torques).  Either of ``force`` /
+    ``torque`` may be None (zero), not both.  ``composed``: as for link_motion."""
+    lib = _lib_of(q, "q", ops_f)
+    q = _dev_f32(q, "q", n_dofs)
+    B = int(q.shape[0])
+    if force is None and torque is None:
+        raise ValueError("force and torque are both None")
+
+    def wrench(t, name):
+        if t is None:
+            return None
+        if t.ndim != 3 or tuple(t.shape) != (B, n_targets, 3):
+            raise ValueError("%s must be [%d, %d, 3], got %s" % (name, B, n_targets, tuple(t.shape)))
+        return _dev_f32(t.reshape(B, n_targets * 3), name, n_targets * 3)
+    force, torque = wrench(force, "force"), wrench(torque, "torque")
+    (tau,) = _outputs(q.device, (B, n_dofs))
+    if B == 0:
+        return tau
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _scratch(lib, "drm_external_torques", (walk,), B, composed, q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_external_torques(ctypes.byref(walk), q.data_ptr(), ptr(force), ptr(torque), B, n_targets,
+                                        LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(scratch), _stream(q.device)), lib)
+    return tau
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

@@ -30,6 +30,7 @@
 #include "drm_lagrangian.hpp"
 #include "drm_idd.hpp"
 #include "drm_energy.hpp"
+#include "drm_links.hpp"
 #include "drm_rollout.hpp"
 #include "drm_rows.hpp"
 
@@ -341,6 +342,93 @@ void energy_host_rows(const drm_walk *w, const float *q, const float *qd, int64_
             });
     }
 }
+// the walks drm_links.hip's fused kernels take: a serial 7-DoF arm chain of 8 ops, every op a target in walk order.  The host build
+// runs their straight-line arithmetic (drm_links.hpp link_chain_*) on every row of such a call, the general walk with DRM_LINKS_COMPOSED.
+bool links_chain_walk(const drm_walk *w, int T, int flags) {
+    return !(flags & DRM_LINKS_COMPOSED) && (w->shape & DRM_WALK_ARM_CHAIN) && (w->shape & DRM_WALK_TARGETS_ORDERED) && w->capacity == 8 &&
+           w->n_dofs == 7 && w->n_ops == 8 && T == 8;
+}
+// drm_link_motion, rows [b0, b0 + rows)
+template <int MODE>
+void link_motion_host_rows(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t b0, int64_t rows, int T, int flags,
+                           float *pos, float *lv, float *av, float *la, float *aa) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    HostRecords<drm::LINKS_SLOT_FLOATS> slots(n_slots);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const bool chain = links_chain_walk(w, T, flags);
+    auto row = [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; };
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = (MODE >= 1 && qd) ? qd + b * n : nullptr, *qddr = (MODE >= 2 && qdd) ? qdd + b * n : nullptr;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::links_bad_input(qr[d], qdr ? qdr[d] : 0.0f, qddr ? qddr[d] : 0.0f);
+        auto emit = [&](int t, const drm::LinkState &st) {
+            if (t >= T) return;
+            const int64_t at = (b * T + t) * 3;
+            for (int i = 0; i < 3; ++i) {
+                if (pos) pos[at + i] = bad ? nan : st.p[i];
+                if (MODE >= 1 && lv) lv[at + i] = bad ? nan : st.v[i];
+                if (MODE >= 1 && av) av[at + i] = bad ? nan : st.w[i];
+                if (MODE >= 2 && la) la[at + i] = bad ? nan : st.a[i];
+                if (MODE >= 2 && aa) aa[at + i] = bad ? nan : st.al[i];
+            }
+        };
+        if (chain) {
+            float qv[7], qdv[7], qddv[7], cs[7], sn[7];
+            for (int d = 0; d < 7; ++d) {
+                qv[d] = bad ? 0.0f : qr[d];
+                qdv[d] = (bad || !qdr) ? 0.0f : qdr[d];
+                qddv[d] = (bad || !qddr) ? 0.0f : qddr[d];
+            }
+            drm::chain_trig<7>(qv, cs, sn);
+            drm::link_chain_motion<8, 7, (MODE >= 1), (MODE >= 2)>(row, cs, sn, qdv, qddv, emit);
+            continue;
+        }
+        drm::link_motion_walk<(MODE >= 1), (MODE >= 2)>(
+            n_ops, n_slots, ctl, row,
+            [&](int d, float &a, float &v, float &acc) {
+                a = bad ? 0.0f : qr[d];
+                v = (bad || !qdr) ? 0.0f : qdr[d];
+                acc = (bad || !qddr) ? 0.0f : qddr[d];
+            },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, emit);
+    }
+}
+// drm_external_torques, rows [b0, b0 + rows)
+void link_torques_host_rows(const drm_walk *w, const float *q, const float *force, const float *torque, int64_t b0, int64_t rows, int T,
+                            int flags, float *tau) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    HostRecords<drm::LINKS_REC_FLOATS> rec(n_ops); HostRecords<drm::LINKS_SLOT_FLOATS> slots(n_slots);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const bool chain = links_chain_walk(w, T, flags);
+    auto row = [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; };
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *fr = force ? force + b * T * 3 : nullptr, *mr = torque ? torque + b * T * 3 : nullptr;
+        float *tr = tau + b * n;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(qr[d], 0.0f);
+        for (int d = 0; d < n; ++d) tr[d] = bad ? nan : 0.0f;
+        auto wrench = [&](int t, float *f, float *m) {
+            for (int i = 0; i < 3; ++i) {
+                f[i] = (fr && t < T) ? fr[3 * t + i] : 0.0f;
+                m[i] = (mr && t < T) ? mr[3 * t + i] : 0.0f;
+            }
+        };
+        auto jout = [&](int j, float v) { if (j < n) tr[j] = bad ? nan : v; };
+        if (chain) {
+            float qv[7], cs[7], sn[7];
+            for (int d = 0; d < 7; ++d) qv[d] = bad ? 0.0f : qr[d];
+            drm::chain_trig<7>(qv, cs, sn);
+            drm::link_chain_torques<8, 7>(row, cs, sn, wrench, jout);
+            continue;
+        }
+        drm::link_torques_walk(
+            n_ops, n_slots, ctl, row, [&](int d) { return bad ? 0.0f : qr[d]; },
+            [&](int k, const float *x) { rec.put(k, x); }, [&](int k, float *x) { rec.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, wrench, jout);
+    }
+}
 } // namespace
 
 extern "C" {
@@ -622,6 +710,41 @@ int drm_energy(const drm_walk *w, const float *q, const float *qd, int64_t B, in
     if (!T && !V && !p && !dT && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { energy_host_rows(w, q, qd, b0, rows, T, V, p, dT, g); });
+    return DRM_OK;
+}
+
+// Link motion and external-wrench torques: every row runs drm_links.hpp's arithmetic — the chain form where drm_links.hip would launch
+// its fused kernels, the general walk elsewhere — without the state in LDS / scratch.
+int64_t drm_link_motion_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_link_motion_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+int64_t drm_external_torques_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_external_torques_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_link_motion(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t T, int32_t flags, float *pos,
+                    float *lv, float *av, float *la, float *aa, float *, void *) {
+    if (int rc = check_sweep_walk(w)) return rc;
+    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
+    if (!pos && !lv && !av && !la && !aa) return fail(DRM_ERR_INVALID, "every output is NULL");
+    const int mode = (la || aa) ? 2 : (lv || av) ? 1 : 0;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        if (mode == 2) link_motion_host_rows<2>(w, q, qd, qdd, b0, rows, T, flags, pos, lv, av, la, aa);
+        else if (mode == 1) link_motion_host_rows<1>(w, q, qd, qdd, b0, rows, T, flags, pos, lv, av, la, aa);
+        else link_motion_host_rows<0>(w, q, qd, qdd, b0, rows, T, flags, pos, lv, av, la, aa);
+    });
+    return DRM_OK;
+}
+
+int drm_external_torques(const drm_walk *w, const float *q, const float *force, const float *torque, int64_t B, int32_t T, int32_t flags,
+                         float *tau, float *, void *) {
+    if (int rc = check_sweep_walk(w)) return rc;
+    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
+    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
+    if (!tau) return fail(DRM_ERR_INVALID, "tau must not be NULL");
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { link_torques_host_rows(w, q, force, torque, b0, rows, T, flags, tau); });
     return DRM_OK;
 }
 

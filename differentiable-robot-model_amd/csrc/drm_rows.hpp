@@ -1,5 +1,5 @@
 // drm_rows.hpp — what the general ("rows") kernels of the tree-sweep entry points share: drm_regressor.hip, drm_lagrangian.hip,
-// drm_idd.hip and drm_energy.hip, and the record layout of their host loops in drm_cpu.cpp.
+// drm_idd.hip, drm_energy.hip and drm_links.hip, and the record layout of their host loops in drm_cpu.cpp.
 //
 // A rows kernel walks rows [0, B) in tiles of 64, one lane per row, and between its sweeps a row keeps `state_floats` floats (records
 // per op, parked composites per branch point) in the layout [float][64 lanes].  WHERE they live is decided here and nowhere else:

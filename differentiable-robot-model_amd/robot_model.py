@@ -27,7 +27,7 @@ from . import backend
 from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, RobotSpec, WalkProgram, build_robot_spec, build_walk, fold_link_table,
                       foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
-                       _ForwardDynamicsRollout, _Energy, _quat_grad_to_rot)
+                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _quat_grad_to_rot)
 from .rigid_body import DifferentiableRigidBody, LinkPose, LinkVelocity
 from .urdf_utils import URDFRobotModel
 
@@ -155,6 +155,15 @@ class Energy(NamedTuple):
     """What DifferentiableRobotModel.compute_energy returns: differentiable once with respect to q and qd."""
     kinetic: torch.Tensor               # [B]
     potential: torch.Tensor             # [B]
+
+
+class LinkMotion(NamedTuple):
+    """What DifferentiableRobotModel.compute_link_motion returns (no autograd history on any field): world axes, at the link origins."""
+    position: torch.Tensor                          # [B, L, 3] the link origins
+    linear_velocity: torch.Tensor                   # [B, L, 3] lin_jac_l qd
+    angular_velocity: torch.Tensor                  # [B, L, 3] ang_jac_l qd
+    linear_acceleration: Optional[torch.Tensor]     # [B, L, 3] d/dt linear_velocity (gravity not included); None when qdd is None
+    angular_acceleration: Optional[torch.Tensor]    # [B, L, 3] d/dt angular_velocity; None when qdd is None
 
 
 class DifferentiableRobotModel(torch.nn.Module):
@@ -1838,6 +1847,165 @@ class DifferentiableRobotModel(torch.nn.Module):
             return _Energy.apply(q, qd, dw.program, ops_f, dw.ops_i, self._n_dofs)
         with torch.no_grad():
             return backend.energy(dw.program, ops_f, dw.ops_i, q.detach(), qd.detach(), self._n_dofs, want=("kinetic", "potential"))[:2]
+
+    # ------------------------------------------------------------------ link motion and external wrenches
+    def _links_plan(self, link_names):
+        """(walk of the distinct non-root links in pre-order, T, sel, identity) for a list of link names (None: every link, root
+        included): ``sel`` [L] maps the caller's position to the walk's output slot, T for the root (a column of zeros that the
+        gather appends, a wrench that the scatter drops); ``identity``: the caller's order IS the walk's, nothing to move."""
+        key = None if link_names is None else tuple(link_names)
+        plans = self.__dict__.setdefault("_links_plans", {})
+        plan = plans.get(key)
+        if plan is None:
+            names = self.get_link_names() if link_names is None else list(link_names)
+            idxs = [self._name_to_idx_map[name] for name in names]
+            wanted = set(i for i in idxs if i != 0)
+            ordered = [i for i in self._spec.preorder() if i in wanted]
+            if not ordered:
+                raise ValueError("link_names must name at least one link besides the root")
+            slot = {i: t for t, i in enumerate(ordered)}
+            sel = [slot.get(i, len(ordered)) for i in idxs]
+            plan = plans[key] = (tuple(ordered), len(ordered), torch.tensor(sel, dtype=torch.int64, device=self._device),
+                                 sel == list(range(len(ordered))))
+        ordered, T, sel, identity = plan
+        return self._get_walk(("fk", ordered), targets=list(ordered)), T, sel, identity
+
+    @staticmethod
+    def _links_gather(x, sel, identity):
+        """[B, T, 3] in walk order -> [B, L, 3] in the caller's order (zeros for the root)"""
+        if x is None or identity:
+            return x
+        return torch.cat([x, x.new_zeros(x.shape[0], 1, 3)], dim=1).index_select(1, sel)
+
+    @staticmethod
+    def _links_scatter(x, sel, T, identity):
+        """[B, L, 3] in the caller's order -> [B, T, 3] in walk order (repeats add up, the root's entry is dropped)"""
+        if x is None or identity:
+            return x
+        return x.new_zeros(x.shape[0], T + 1, 3).index_add_(1, sel, x)[:, :T]
+
+    def _links_args(self, q, others, trailing):
+        """The argument handling of tensor_check for tensors whose trailing shape is not [n]: ``others`` are (tensor or None, name)
+        with trailing shape ``trailing`` after q's batch shape.  Returns (unbatched, q [B, n], others batched)."""
+        tensors = [(q, "q")] + [(t, name) for t, name in others if t is not None]
+        for t, name in tensors:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a tensor" % name)
+            assert t.device.type == self._device.type, f"Input argument of different device as module: {name}"
+        assert q.ndim in [1, 2], "Input tensors must have ndim of 1 or 2."
+        unbatched = q.ndim == 1
+        batch = tuple(q.shape[:-1])
+        assert q.shape[-1] == self._n_dofs
+        out = []
+        for t, name in others:
+            if t is not None:
+                assert tuple(t.shape) == batch + tuple(trailing), "%s must be %s, got %s" % (name, batch + tuple(trailing), tuple(t.shape))
+                t = t.unsqueeze(0) if unbatched else t
+            out.append(t)
+        return unbatched, (q.unsqueeze(0) if unbatched else q), out
+
+    def _refuse_grad_q(self, q, what):
+        if torch.is_grad_enabled() and q.requires_grad:
+            raise ValueError("%s has no gradient with respect to q (it needs the kinematic Hessian, which is out of scope): "
+                             "pass q.detach()" % what)
+
+    def compute_link_motion(self, q: torch.Tensor, qd: torch.Tensor, qdd: Optional[torch.Tensor] = None,
+                            link_names: Optional[List[str]] = None, *, _composed: bool = False) -> LinkMotion:
+        """Position, velocity and classical acceleration of the named links (None: every link in get_link_names() order, the root
+        included) at q, qd, qdd [B, n], in the frame of compute_endeffector_jacobian — WORLD axes, at the link frame's origin.  With
+        lin_jac_l, ang_jac_l that method's outputs for link l:
+            position              [B, L, 3]  the link origin (compute_forward_kinematics' position up to float32 rounding)
+            linear_velocity       [B, L, 3]  lin_jac_l qd
+            angular_velocity      [B, L, 3]  ang_jac_l qd
+            linear_acceleration   [B, L, 3]  d/dt linear_velocity = lin_jac_l qdd + d(lin_jac_l)/dt qd: the classical acceleration of
+                                             the origin, what an accelerometer there reads once gravity is added (it is NOT included)
+                                             and the bias term of a contact constraint; None when qdd is None
+            angular_acceleration  [B, L, 3]  d/dt angular_velocity; None when qdd is None
+        ``link_names`` may be any list: any order, repeats, the root (which gets zeros).  Link orientation is
+        compute_forward_kinematics_links'; body-frame outputs are out of scope.
+
+        ONE kernel launch (csrc/drm_links.hip drm_link_motion): a world-frame sweep outwards over the many-target walk of the distinct
+        non-root links, instead of one compute_endeffector_jacobian launch and two einsums per link.  All 8 links of a 7-DoF arm: a
+        kernel that keeps everything in registers on full 64-row tiles; every other robot and link set one lane per row over the ops.
+        Together with compute_external_torques it enters the existing entry points exactly, by linearity:
+            tau = compute_inverse_dynamics(q, qd, qdd) - tau_ext          qdd = compute_forward_dynamics(q, qd, f + tau_ext).
+        Argument handling is that of the neighbours (unbatched inputs give unbatched results); works on the CPU and on a HIP device,
+        with either joint model and for models with learnable links (their current values are used).  A row whose q, qd or qdd is
+        not finite, or whose |q| is beyond 1e5, returns NaN in every output and changes no bit of any other row.  The results carry
+        NO autograd history (compute_link_velocities is differentiable in qd).  (``_composed``, or DRM_LINKS_COMPOSED=1 in the
+        environment: every row takes the general kernel; for tests and A/B measurements.)"""
+        unbatched, q, (qd, qdd) = self._links_args(q, [(qd, "qd"), (qdd, "qdd")], (self._n_dofs,))
+        assert qd is not None, "qd must be given"
+        self._require_device()
+        with torch.no_grad():
+            dw, T, sel, identity = self._links_plan(link_names)
+            want = backend.LINK_MOTION_OUTPUTS[:3 if qdd is None else 5]
+            outs = backend.link_motion(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(),
+                                       None if qdd is None else qdd.detach(), T, self._n_dofs, want=want, composed=bool(_composed))
+            outs = [self._links_gather(x, sel, identity) for x in outs]
+        return LinkMotion(*[x[0] if (unbatched and x is not None) else x for x in outs])
+
+    def compute_link_velocities(self, q: torch.Tensor, qd: torch.Tensor, link_names: Optional[List[str]] = None, *,
+                                _composed: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(linear_velocity, angular_velocity) [B, L, 3] of compute_link_motion(q, qd, link_names=link_names), to the bit, from the same
+        launch with the two velocity arrays alone requested — and DIFFERENTIABLE once with respect to qd: the backward is the
+        compute_external_torques launch with (forces, torques) := (grad_linear, grad_angular) (autograd._LinkAdjoint; a second backward
+        raises).  There is NO gradient with respect to q — it needs the kinematic Hessian, which is out of scope: with grad mode on a q
+        that requires grad raises ValueError; pass q.detach()."""
+        unbatched, q, (qd,) = self._links_args(q, [(qd, "qd")], (self._n_dofs,))
+        assert qd is not None, "qd must be given"
+        self._refuse_grad_q(q, "compute_link_velocities")
+        self._require_device()
+        with torch.no_grad():
+            dw, T, sel, identity = self._links_plan(link_names)
+            ops_f = self._ops_f(dw).detach()
+        if torch.is_grad_enabled() and qd.requires_grad:
+            lin, ang = _LinkAdjoint.apply(False, q.detach(), qd, None, dw.program, ops_f, dw.ops_i, T, self._n_dofs, bool(_composed))
+        else:
+            with torch.no_grad():
+                out = backend.link_motion(dw.program, ops_f, dw.ops_i, q.detach(), qd.detach(), None, T, self._n_dofs,
+                                          want=("linear_velocity", "angular_velocity"), composed=bool(_composed))
+            lin, ang = out[1], out[2]
+        lin, ang = self._links_gather(lin, sel, identity), self._links_gather(ang, sel, identity)
+        return (lin[0], ang[0]) if unbatched else (lin, ang)
+
+    def compute_external_torques(self, q: torch.Tensor, forces: Optional[torch.Tensor], torques: Optional[torch.Tensor] = None,
+                                 link_names: Optional[List[str]] = None, *, _composed: bool = False) -> torch.Tensor:
+        """tau_ext [B, n] = sum_l lin_jac_l^T forces[:, l] + ang_jac_l^T torques[:, l]: the joint torques of external wrenches on the
+        named links (None: every link in get_link_names() order) — contact forces, a payload, a wrist force/torque reading — with
+        lin_jac_l, ang_jac_l compute_endeffector_jacobian's outputs for link l.  ``forces`` / ``torques`` [B, L, 3] are in WORLD axes
+        and a force acts at the link frame's ORIGIN; a force at another point is the caller's torques += r x f.  Either may be None
+        (zero), not both.  ``link_names`` may be any list: repeats add up, a wrench on the root is ignored.  Columns of joints that no
+        named link's chain crosses are zero.  External wrenches enter the existing entry points exactly, by linearity:
+            tau = compute_inverse_dynamics(q, qd, qdd) - tau_ext          qdd = compute_forward_dynamics(q, qd, f + tau_ext).
+
+        ONE kernel launch (csrc/drm_links.hip drm_external_torques): a sweep outwards for the poses and one inwards for the wrenches,
+        instead of one Jacobian launch and two einsums per loaded link.  It is the adjoint of compute_link_velocities:
+        sum_l f_l . v_l + m_l . w_l == tau_ext . qd for every qd.  DIFFERENTIABLE once with respect to forces and torques: the backward
+        is the link-motion launch with qd := grad_tau (autograd._LinkAdjoint; a second backward raises).  There is NO gradient with
+        respect to q — it needs the kinematic Hessian, which is out of scope: with grad mode on a q that requires grad raises
+        ValueError; pass q.detach().  A row whose q is not finite (or beyond 1e5) returns NaN and changes no other row; a wrench
+        component that is not finite makes the torques of that link's ancestor joints non-finite and changes nothing else.  Devices,
+        joint models, learnable links and ``_composed``: as for compute_link_motion."""
+        if forces is None and torques is None:
+            raise ValueError("forces and torques are both None")
+        with torch.no_grad():
+            dw, T, sel, identity = self._links_plan(link_names)
+        unbatched, q, (forces, torques) = self._links_args(q, [(forces, "forces"), (torques, "torques")], (int(sel.numel()), 3))
+        self._refuse_grad_q(q, "compute_external_torques")
+        self._require_device()
+        with torch.no_grad():
+            ops_f = self._ops_f(dw).detach()
+        needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (forces, torques))
+        with torch.set_grad_enabled(needs_grad):
+            f, m = self._links_scatter(forces, sel, T, identity), self._links_scatter(torques, sel, T, identity)
+        if needs_grad:
+            tau = _LinkAdjoint.apply(True, q.detach(), f, m, dw.program, ops_f, dw.ops_i, T, self._n_dofs, bool(_composed))
+        else:
+            with torch.no_grad():
+                tau = backend.external_torques(dw.program, ops_f, dw.ops_i, q.detach(), f.detach() if f is not None else None,
+                                               m.detach() if m is not None else None, T, self._n_dofs, composed=bool(_composed))
+        return tau[0] if unbatched else tau
 
     def compute_inverse_dynamics_derivatives(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor,
                                              include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False, *,

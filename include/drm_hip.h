@@ -665,6 +665,52 @@ int drm_energy(const drm_walk *walk, const float *q, const float *qd, int64_t B,
                float *g, float *scratch, void *stream);
 
 /*
+ * Positions, velocities and classical accelerations of T links in ONE call (ABI 15, additive), and the joint torques of external
+ * wrenches on T links in ONE call: what a caller otherwise composes from one drm_fk_jacobian launch and two small products PER LINK
+ * (168 B per row of Jacobian, thrown away after one product).  `walk` is a MANY-TARGET FK walk (flatten.build_walk(targets=...), what
+ * drm_fk takes): target t is the op whose DRM_OPI_OUT == t, fixed links that are targets are ops of their own, parents are
+ * DRM_OPI_W1's.  The dynamics walk is not taken: it folds fixed links away.
+ * Frame: drm_fk_jacobian's — WORLD axes, at the link frame's origin.  With lin_jac_t / ang_jac_t that call's outputs for link t:
+ *   pos      [B, T, 3]  the link origin (drm_fk's position up to float32 rounding)
+ *   lin_vel  [B, T, 3]  lin_jac_t qd                   ang_vel  [B, T, 3]  ang_jac_t qd
+ *   lin_acc  [B, T, 3]  d/dt lin_vel = lin_jac_t qdd + d(lin_jac_t)/dt qd, the classical acceleration of the origin; gravity is NOT
+ *                       included                        ang_acc  [B, T, 3]  d/dt ang_vel
+ *   tau      [B, n]     sum_t lin_jac_t^T force[:, t] + ang_jac_t^T torque[:, t]; a force acts at the link ORIGIN (a force at another
+ *                       point is the caller's torque += r x f).  Columns of DoFs that no target's chain crosses are written as zeros.
+ * One world-frame sweep outwards (csrc/drm_links.hpp), for the torques followed by one inwards.  The two are adjoint:
+ * sum_t force_t . lin_vel_t + torque_t . ang_vel_t == tau . qd for every qd, so each is the other's reverse mode.  By linearity
+ * tau = drm_rnea(q, qd, qdd) - tau_ext balances external wrenches and qdd = drm_forward_dynamics(q, qd, f + tau_ext) applies them.
+ *   drm_link_motion        q [B, n]; qd NULL => zero (positions alone), qdd NULL => zero (accelerations = Jdot qd); any of the five
+ *                          outputs may be NULL, not all.  With both acceleration outputs NULL the acceleration terms are not formed,
+ *                          with the velocity outputs NULL too neither are the velocity terms.
+ *   drm_external_torques   force, torque [B, T, 3], either NULL (= zero), not both; tau [B, n]
+ * A serial 7-DoF arm chain of 8 ops (DRM_WALK_ARM_CHAIN, capacity 8) whose 8 ops are all targets in walk order
+ * (DRM_WALK_TARGETS_ORDERED, n_targets == 8), full 64-row tiles, 16-byte aligned pointers and table: fused kernels, one wavefront per
+ * tile, one row per lane, everything in registers, every tile through LDS in 16-byte accesses (84 B in, up to 480 B out per row; 220 B
+ * in, 28 B out).  Every other walk (trees, hands, prismatic joints, two-op skew-axis links, target subsets), the ragged tail,
+ * misaligned pointers and DRM_LINKS_COMPOSED: one lane per row, loops over the ops.
+ * A row with a q, qd or qdd that is not finite, or with a |q| beyond 1e5, is walked at rest at q = 0, gets NaN in every output that is
+ * written and changes no bit of any other row.  A wrench component that is not finite makes the torques of that link's ancestor
+ * joints non-finite and changes nothing else.
+ *   scratch   the matching _scratch_floats query's floats (the _aligned form returns the same): the rows' state where 64 rows of it do
+ *             not fit the general kernels' LDS budget — motion 24 floats per branch point, torques 12 n_ops + 24 n_slots floats per
+ *             row, at most 2 048 tiles of 64 rows at a time; 0 (scratch may be NULL) for drm_link_motion of walks of up to 5 branch
+ *             points and for drm_external_torques of chains of up to 10 ops
+ * DRM_ERR_INVALID for a NULL q, no output (no wrench input; a NULL tau), a negative B, or an n_targets that cannot be the walk's number
+ * of output slots (outside [1, n_ops]; slots beyond n_targets are neither read nor written); B == 0 returns DRM_OK.  Asynchronous on
+ * `stream`, never a host synchronisation, no allocation.
+ */
+#define DRM_LINKS_COMPOSED 1024     /* force the general kernel on every row (tests, A/B) */
+int64_t drm_link_motion_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_link_motion_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int64_t drm_external_torques_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_external_torques_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_link_motion(const drm_walk *walk, const float *q, const float *qd, const float *qdd, int64_t B, int32_t n_targets, int32_t flags,
+                    float *pos, float *lin_vel, float *ang_vel, float *lin_acc, float *ang_acc, float *scratch, void *stream);
+int drm_external_torques(const drm_walk *walk, const float *q, const float *force, const float *torque, int64_t B, int32_t n_targets,
+                         int32_t flags, float *tau, float *scratch, void *stream);
+
+/*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
  * compute_forward_kinematics' outputs is back-propagated to q and to learnable `trans` / `rot_angles`
  * (robot_model.py:139-195, 223-248, 669-713; examples/learn_kinematics_of_iiwa.py:25-61).
