@@ -2600,13 +2600,15 @@ DRM_HD void inertia_to_parent(const float *J, const float *t, const Inertia &c, 
     auto R = [&](int r, int k) { return M[r * 3 + 0] * J[k * 3 + 0] + M[r * 3 + 1] * J[k * 3 + 1] + M[r * 3 + 2] * J[k * 3 + 2]; };
 #pragma unroll
     for (int i = 0; i < 3; ++i) w[i] = g[i] + 0.5f * c.m * t[i];
-    const float wt2 = 2.0f * (w[0] * t[0] + w[1] * t[1] + w[2] * t[2]);
-    out.I[0] = R(0, 0) + (wt2 - 2.0f * w[0] * t[0]);
+    // the diagonal of 2 (w . t) E - w t^T - t w^T entry by entry, 2 (w_j t_j + w_k t_k): taking w_i t_i out of the full dot product
+    // again cancels where the offset lies along the axis (a roll joint's own H[k][k]) and leaves an ulp of the large product behind
+    const float p[3] = {w[0] * t[0], w[1] * t[1], w[2] * t[2]};
+    out.I[0] = R(0, 0) + 2.0f * (p[1] + p[2]);
     out.I[1] = R(0, 1) - (w[0] * t[1] + t[0] * w[1]);
     out.I[2] = R(0, 2) - (w[0] * t[2] + t[0] * w[2]);
-    out.I[3] = R(1, 1) + (wt2 - 2.0f * w[1] * t[1]);
+    out.I[3] = R(1, 1) + 2.0f * (p[0] + p[2]);
     out.I[4] = R(1, 2) - (w[1] * t[2] + t[1] * w[2]);
-    out.I[5] = R(2, 2) + (wt2 - 2.0f * w[2] * t[2]);
+    out.I[5] = R(2, 2) + 2.0f * (p[0] + p[1]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) out.h[i] = g[i] + c.m * t[i];
     out.m = c.m;
@@ -2794,13 +2796,14 @@ DRM_HD void inertia2_to_parent(const Joint2 &J, const float *F, const float *t, 
     auto R = [&](int r, int k) { return M[r * 3 + 0] * J.c0[k] + M[r * 3 + 1] * J.c1[k] + M[r * 3 + 2] * f2_bcast(F[k * 3 + 2]); };
 #pragma unroll
     for (int i = 0; i < 3; ++i) w[i] = g[i] + f2_bcast(0.5f * c.m * t[i]);
-    const f2 wt2 = f2_bcast(2.0f) * (w[0] * f2_bcast(t[0]) + w[1] * f2_bcast(t[1]) + w[2] * f2_bcast(t[2]));
-    out.I[0] = R(0, 0) + (wt2 - f2_bcast(2.0f * t[0]) * w[0]);
+    // (the diagonal entry by entry, as in inertia_to_parent: no w_i t_i taken out of the full dot product again)
+    const f2 p[3] = {w[0] * f2_bcast(t[0]), w[1] * f2_bcast(t[1]), w[2] * f2_bcast(t[2])};
+    out.I[0] = R(0, 0) + f2_bcast(2.0f) * (p[1] + p[2]);
     out.I[1] = R(0, 1) - (w[0] * f2_bcast(t[1]) + f2_bcast(t[0]) * w[1]);
     out.I[2] = R(0, 2) - (w[0] * f2_bcast(t[2]) + f2_bcast(t[0]) * w[2]);
-    out.I[3] = R(1, 1) + (wt2 - f2_bcast(2.0f * t[1]) * w[1]);
+    out.I[3] = R(1, 1) + f2_bcast(2.0f) * (p[0] + p[2]);
     out.I[4] = R(1, 2) - (w[1] * f2_bcast(t[2]) + f2_bcast(t[1]) * w[2]);
-    out.I[5] = R(2, 2) + (wt2 - f2_bcast(2.0f * t[2]) * w[2]);
+    out.I[5] = R(2, 2) + f2_bcast(2.0f) * (p[0] + p[1]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) out.h[i] = g[i] + f2_bcast(c.m * t[i]);
     out.m = c.m;

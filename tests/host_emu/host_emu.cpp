@@ -206,6 +206,27 @@ void rneab_arm_hand_emu(const drm_walk *w, int K, const float *q, const float *q
 }
 
 
+// the arithmetic of forward_dynamics_arm_kernel<8, 7, LINKS>: bias torques by rnea_chain_trig with qdd = 0, H's lower triangle by
+// crba_chain_trig on the same cos / sin, the unrolled L^T D L solve; LINKS = 7 (fixed tail folded) or 8 (the whole table)
+template <int LINKS>
+void fd_arm_8_7(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int flags, float *qdd) {
+    constexpr int NJ = 7;
+    auto row = [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; };
+    for (int64_t b = 0; b < B; ++b) {
+        float qv[NJ], qdv[NJ], rhs[NJ], zero[NJ], nle[NJ], cs[NJ], sn[NJ];
+        for (int d = 0; d < NJ; ++d) { qv[d] = q[b * NJ + d]; qdv[d] = qd[b * NJ + d]; rhs[d] = f[b * NJ + d]; zero[d] = 0.f; }
+        chain_trig<NJ>(qv, cs, sn);
+        Force park[8];
+        rnea_chain_trig<LINKS, NJ>(row, flags & DRM_RNEA_GRAVITY, flags & DRM_RNEA_DAMPING, cs, sn, qdv, zero, nle,
+                                   [&](int k, const Force &F) { park[k] = F; }, [&](int k, Force &F) { F = park[k]; });
+        float Ht[NJ * (NJ + 1) / 2];
+        crba_chain_trig<LINKS, NJ>(row, cs, sn, [&](int i, int j, float v) { if (i >= j) Ht[tri_index(i, j)] = v; });
+        for (int d = 0; d < NJ; ++d) rhs[d] -= nle[d];
+        ltdl_solve_unrolled<NJ>(Ht, rhs);
+        for (int d = 0; d < NJ; ++d) qdd[b * NJ + d] = rhs[d];
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -290,6 +311,12 @@ int emu_rnea_backward(const drm_walk *w, const float *q, const float *qd, const 
 int emu_forward_dynamics(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int32_t flags,
                          float *qdd) {
     fd_loop(w, q, qd, f, B, flags, qdd);
+    return 0;
+}
+int emu_forward_dynamics_arm(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int32_t flags, float *qdd) {
+    if (!(w->shape & DRM_WALK_ARM_CHAIN) || w->capacity != 8 || w->n_dofs != 7) return -2;
+    if (w->n_ops == 7) fd_arm_8_7<7>(w, q, qd, f, B, flags, qdd);
+    else fd_arm_8_7<8>(w, q, qd, f, B, flags, qdd);
     return 0;
 }
 int emu_link_rows(const float *params, int32_t n, float *rows) {
