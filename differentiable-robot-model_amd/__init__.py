@@ -19,6 +19,10 @@ from .robot_model import (  # noqa: F401
     EnergyDerivatives,
     Energy,
     LinkMotion,
+    PlaneContact,
+    JointLimitSprings,
+    ContactTorques,
+    ContactRollout,
 )
 
 __version__ = "0.1.0"

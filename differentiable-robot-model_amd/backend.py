@@ -60,6 +60,17 @@ class DrmPut(ctypes.Structure):
                 ("tau", ctypes.c_void_p * MAX_PEERS), ("pos", ctypes.c_void_p * MAX_PEERS), ("quat", ctypes.c_void_p * MAX_PEERS)]
 
 
+class DrmContactPlane(ctypes.Structure):
+    """Mirror of ``struct drm_contact_plane`` (include/drm_hip.h)."""
+    _fields_ = [("normal", ctypes.c_float * 3), ("offset", ctypes.c_float), ("stiffness", ctypes.c_float), ("damping", ctypes.c_float),
+                ("friction", ctypes.c_float), ("friction_slope", ctypes.c_float)]
+
+
+class DrmJointSprings(ctypes.Structure):
+    """Mirror of ``struct drm_joint_springs`` (include/drm_hip.h)."""
+    _fields_ = [("stiffness", ctypes.c_float), ("damping", ctypes.c_float)]
+
+
 FK_MSE_MAX_LINKS = 8
 
 
@@ -102,7 +113,9 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_rnea_derivatives", "drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned",
            "drm_energy", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
            "drm_link_motion", "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
-           "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned")
+           "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
+           "drm_contact_torques", "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
+           "drm_contact_rollout", "drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -204,9 +217,18 @@ def load_library(path: str = None, kind: str = "cuda"):
                      "drm_lagrangian_dynamics_scratch_floats_aligned", "drm_rnea_derivatives_scratch_floats",
                      "drm_rnea_derivatives_scratch_floats_aligned", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
                      "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
-                     "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned"):
+                     "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
+                     "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
+        for name in ("drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, wp, i64]
+        pp, sp = ctypes.POINTER(DrmContactPlane), ctypes.POINTER(DrmJointSprings)
+        lib.drm_contact_torques.restype = ctypes.c_int
+        lib.drm_contact_torques.argtypes = [wp, vp, vp, i64, i32, pp, vp, sp, vp, vp, i32, vp, vp, vp, vp, vp]
+        lib.drm_contact_rollout.restype = ctypes.c_int
+        lib.drm_contact_rollout.argtypes = [wp, wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, i32, pp, vp, sp, vp, vp, vp, vp, vp, vp, vp]
         lib.drm_operational_space.restype = ctypes.c_int
         lib.drm_operational_space.argtypes = [wp, wp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]
         for name in ("drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned"):
@@ -1204,6 +1226,102 @@ def external_torques(prog: WalkProgram, ops_f, ops_i, q, force, torque, n_target
         _check(lib.drm_external_torques(ctypes.byref(walk), q.data_ptr(), ptr(force), ptr(torque), B, n_targets,
                                         LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(scratch), _stream(q.device)), lib)
     return tau
+
+
+def _contact_structs(plane, radius, springs, n_targets: int, n_dofs: int, device):
+    """(drm_contact_plane or None, radius tensor or None, drm_joint_springs or None, lower, upper) of the contact arguments:
+    ``plane`` (normal [3], offset, stiffness, damping, friction, friction_slope), ``radius`` [n_targets] on ``device`` or None,
+    ``springs`` (stiffness, damping, lower [n], upper [n]) with the bounds on ``device``.  The C side validates the values."""
+    pl = None
+    if plane is not None:
+        normal, offset, k, c, mu, ct = plane
+        pl = DrmContactPlane((ctypes.c_float * 3)(*[float(x) for x in normal]), float(offset), float(k), float(c), float(mu), float(ct))
+        if radius is not None:
+            if radius.device != device or radius.dtype != torch.float32 or tuple(radius.shape) != (n_targets,) or not radius.is_contiguous():
+                raise ValueError("radius must be a contiguous float32 [%d] on %s" % (n_targets, device))
+    else:
+        radius = None
+    sp = lower = upper = None
+    if springs is not None:
+        k, c, lower, upper = springs
+        sp = DrmJointSprings(float(k), float(c))
+        for name, t in (("lower", lower), ("upper", upper)):
+            if t.device != device or t.dtype != torch.float32 or tuple(t.shape) != (n_dofs,) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 [%d] on %s" % (name, n_dofs, device))
+    return pl, radius, sp, lower, upper
+
+
+def contact_torques(prog: WalkProgram, ops_f, ops_i, q, qd, n_targets: int, n_dofs: int, plane, radius=None, springs=None,
+                    want_wrenches: bool = True, composed: bool = False):
+    """(tau [B, n], force [B, T, 3], moment [B, T, 3]): the joint torques of the plane's contact with spheres on the T targets of a
+    many-target FK walk, plus joint-limit springs, and the wrenches at the link origins (include/drm_hip.h drm_contact_torques;
+    None with ``want_wrenches`` False).  ``plane`` / ``radius`` / ``springs``: _contact_structs.  ``composed``: as for link_motion."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B:
+        raise ValueError("q / qd batch sizes differ")
+    if plane is None:
+        raise ValueError("contact_torques needs a plane")
+    pl, radius, sp, lower, upper = _contact_structs(plane, radius, springs, n_targets, n_dofs, q.device)
+    outs = _outputs(q.device, (B, n_dofs), *([(B, n_targets, 3)] * (2 if want_wrenches else 0)))
+    tau, force, moment = outs[0], (outs[1] if want_wrenches else None), (outs[2] if want_wrenches else None)
+    if B == 0:
+        return tau, force, moment
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _scratch(lib, "drm_contact_torques", (walk,), B, composed, q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_contact_torques(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, n_targets, ctypes.byref(pl), ptr(radius),
+                                       ctypes.byref(sp) if sp is not None else None, ptr(lower), ptr(upper),
+                                       LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(force), ptr(moment), ptr(scratch),
+                                       _stream(q.device)), lib)
+    return tau, force, moment
+
+
+def contact_rollout(dyn, links, q0, qd0, tau, dt: float, gravity: bool, damping: bool, explicit: bool, n_targets: int, n_dofs: int,
+                    plane, radius=None, springs=None, want_qdd: bool = False, composed: bool = False):
+    """(q_traj, qd_traj, qdd_traj or None), each [T, B, n]: forward_dynamics_rollout with the plane's contact torques and the
+    joint-limit springs of every step's state added to tau[t] (include/drm_hip.h drm_contact_rollout).  ``dyn`` / ``links``:
+    (program, ops_f, ops_i) of the dynamics walk and of the many-target FK walk of the contact links (``links`` None without a
+    plane).  ``plane`` / ``radius`` / ``springs``: _contact_structs; ``composed``: the composed steps on every row."""
+    lib = _lib_of(q0, "q0", dyn[1])
+    q0, qd0 = _dev_f32(q0, "q0", n_dofs), _dev_f32(qd0, "qd0", n_dofs)
+    if not isinstance(tau, torch.Tensor) or tau.ndim != 3 or tau.shape[2] != n_dofs:
+        raise ValueError("tau must be [T, B, %d], got %s" % (n_dofs, tuple(getattr(tau, "shape", ()))))
+    T, B = int(tau.shape[0]), int(q0.shape[0])
+    if qd0.shape[0] != B or tau.shape[1] != B:
+        raise ValueError("q0 / qd0 / tau batch sizes differ")
+    if T < 1:
+        raise ValueError("a rollout takes at least one step (tau has T = %d)" % T)
+    if not (math.isfinite(dt) and dt > 0):
+        raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+    if plane is None and springs is None:
+        raise ValueError("neither a contact plane nor joint-limit springs: compute_forward_dynamics_rollout is the plain rollout")
+    tau = _dev_f32(tau.reshape(T * B, n_dofs), "tau", n_dofs)
+    pl, radius, sp, lower, upper = _contact_structs(plane, radius, springs, n_targets, n_dofs, q0.device)
+    outs = _outputs(q0.device, *(((T, B, n_dofs),) * (3 if want_qdd else 2)))
+    q_traj, qd_traj = outs[0], outs[1]
+    qdd_traj = outs[2] if want_qdd else None
+    if B == 0:
+        return q_traj, qd_traj, qdd_traj
+    composed = _links_composed(composed)
+    flags = ((RNEA_GRAVITY if gravity else 0) | (RNEA_DAMPING if damping else 0) | (ROLLOUT_EXPLICIT_EULER if explicit else 0) |
+             (LINKS_COMPOSED if composed else 0))
+    dwalk = _walk_struct(dyn[0], dyn[1].detach(), dyn[2], n_dofs)
+    lwalk = _walk_struct(links[0], links[1].detach(), links[2], n_dofs) if pl is not None else None
+    lref = ctypes.byref(lwalk) if lwalk is not None else None
+    query = lib.drm_contact_rollout_scratch_floats if composed else lib.drm_contact_rollout_scratch_floats_aligned
+    need = int(query(ctypes.byref(dwalk), lref, B))
+    scratch = torch.empty(need, device=q0.device, dtype=torch.float32) if need > 0 else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device(q0.device):
+        _check(lib.drm_contact_rollout(ctypes.byref(dwalk), lref, q0.data_ptr(), qd0.data_ptr(), tau.data_ptr(), B, T, float(dt), flags,
+                                       n_targets, ctypes.byref(pl) if pl is not None else None, ptr(radius),
+                                       ctypes.byref(sp) if sp is not None else None, ptr(lower), ptr(upper), q_traj.data_ptr(),
+                                       qd_traj.data_ptr(), ptr(qdd_traj), ptr(scratch), _stream(q0.device)), lib)
+    return q_traj, qd_traj, qdd_traj
 
 
 def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):

@@ -31,6 +31,7 @@
 #include "drm_idd.hpp"
 #include "drm_energy.hpp"
 #include "drm_links.hpp"
+#include "drm_contact.hpp"
 #include "drm_rollout.hpp"
 #include "drm_rows.hpp"
 
@@ -429,6 +430,86 @@ void link_torques_host_rows(const drm_walk *w, const float *q, const float *forc
             [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, wrench, jout);
     }
 }
+// what drm_contact_torques and drm_contact_rollout ask of their contact arguments (drm_contact.hip contact_check)
+struct ContactArgs {
+    drm::ContactPlane pl;
+    bool has_plane;
+    const float *radius;
+    float k, c;
+    const float *lower, *upper; // NULL: no joint-limit springs
+};
+int contact_check(const drm_walk *lw, int64_t B, int T, const drm_contact_plane *plane, const float *radius, const drm_joint_springs *springs,
+                  const float *lower, const float *upper, ContactArgs &a) {
+    a = ContactArgs{};
+    if (!plane && !springs) return fail(DRM_ERR_INVALID, "neither a contact plane nor joint-limit springs");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (plane) {
+        if (int rc = check_sweep_walk(lw)) return rc;
+        if (T < 1 || T > lw->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
+        const int bad = drm::contact_plane_make(plane, a.pl);
+        if (bad == 1) return fail(DRM_ERR_INVALID, "the plane's offset must be finite, its stiffness, damping, friction and slope finite and >= 0");
+        if (bad) return fail(DRM_ERR_INVALID, "the plane's normal must be finite and not zero");
+        a.has_plane = true;
+        a.radius = radius;
+    }
+    if (springs) {
+        if (!drm::joint_springs_ok(springs)) return fail(DRM_ERR_INVALID, "the joint springs' stiffness and damping must be finite and >= 0");
+        if (!lower || !upper) return fail(DRM_ERR_INVALID, "joint springs need lower and upper");
+        a.k = springs->stiffness; a.c = springs->damping; a.lower = lower; a.upper = upper;
+    }
+    return DRM_OK;
+}
+// out = tau_in + (tau_ext + tau_lim) of `rows` rows from q, qd on (all pointers at the first of them; tau_in, force, moment may be
+// NULL): the chain form where drm_contact.hip would launch its fused kernels, elsewhere its composition of the link sweeps and the law.
+// check_rows: a row whose q or qd cannot be used gets NaN (drm_contact_torques).
+void contact_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q, const float *qd, const float *tau_in, int64_t rows, int T,
+                       int n, int flags, bool check_rows, float *out, float *force, float *moment) {
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    std::vector<float> ext((size_t)rows * n, 0.0f);
+    if (a.has_plane && links_chain_walk(lw, T, flags)) {
+        auto row = [&](int k) { return lw->ops_f + k * DRM_OPF_STRIDE; };
+        for (int64_t b = 0; b < rows; ++b) {
+            bool bad = false;
+            for (int d = 0; d < 7; ++d) bad = bad || drm::lag_bad_input(q[b * 7 + d], qd[b * 7 + d]);
+            float qv[7], qdv[7], cs[7], sn[7];
+            for (int d = 0; d < 7; ++d) { qv[d] = bad ? 0.0f : q[b * 7 + d]; qdv[d] = bad ? 0.0f : qd[b * 7 + d]; }
+            drm::chain_trig<7>(qv, cs, sn);
+            drm::contact_chain_torques<8, 7>(
+                row, a.pl, cs, sn, qdv, [&](int k) { return a.radius ? a.radius[k] : 0.0f; },
+                [&](int k, const float *f, const float *m) {
+                    for (int i = 0; i < 3; ++i) {
+                        if (force) force[(b * 8 + k) * 3 + i] = bad ? nan : f[i];
+                        if (moment) moment[(b * 8 + k) * 3 + i] = bad ? nan : m[i];
+                    }
+                },
+                [&](int j, float v) { ext[b * 7 + j] = v; });
+        }
+    } else if (a.has_plane) {
+        const size_t L = (size_t)rows * T * 3;
+        std::vector<float> pos(L), lv(L), av(L), fbuf(force ? 0 : L), mbuf(moment ? 0 : L);
+        float *f = force ? force : fbuf.data(), *m = moment ? moment : mbuf.data();
+        link_motion_host_rows<1>(lw, q, qd, nullptr, 0, rows, T, flags, pos.data(), lv.data(), av.data(), nullptr, nullptr);
+        for (int64_t i = 0; i < rows * T; ++i) {
+            float fi[3], mi[3];
+            drm::contact_wrench(a.pl, a.radius ? a.radius[i % T] : 0.0f, &pos[3 * i], &lv[3 * i], &av[3 * i], fi, mi);
+            const bool bad = pos[3 * i] != pos[3 * i];
+            for (int k = 0; k < 3; ++k) { f[3 * i + k] = bad ? nan : fi[k]; m[3 * i + k] = bad ? nan : mi[k]; }
+        }
+        link_torques_host_rows(lw, q, f, m, 0, rows, T, flags, ext.data());
+    }
+    for (int64_t b = 0; b < rows; ++b) {
+        bool bad = false;
+        if (check_rows)
+            for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(q[b * n + d], qd[b * n + d]);
+        for (int d = 0; d < n; ++d) {
+            const int64_t i = b * n + d;
+            float e = ext[i];
+            if (a.lower) e += drm::joint_spring_torque(a.k, a.c, a.lower[d], a.upper[d], q[i], qd[i]);
+            if (bad) e = nan;
+            out[i] = tau_in ? tau_in[i] + e : e;
+        }
+    }
+}
 } // namespace
 
 extern "C" {
@@ -745,6 +826,62 @@ int drm_external_torques(const drm_walk *w, const float *q, const float *force, 
     if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
     if (!tau) return fail(DRM_ERR_INVALID, "tau must not be NULL");
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { link_torques_host_rows(w, q, force, torque, b0, rows, T, flags, tau); });
+    return DRM_OK;
+}
+
+// Contact torques and contact rollouts (drm_contact.hpp): every chunk of rows runs contact_host_rows, a rollout then fd_loop and the
+// integrator of drm_rollout.hpp per step, the state of step t read back from the slab step t - 1 wrote.
+int64_t drm_contact_torques_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_contact_torques_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+int64_t drm_contact_rollout_scratch_floats(const drm_walk *, const drm_walk *, int64_t) { return 0; }
+int64_t drm_contact_rollout_scratch_floats_aligned(const drm_walk *, const drm_walk *, int64_t) { return 0; }
+
+int drm_contact_torques(const drm_walk *lw, const float *q, const float *qd, int64_t B, int32_t T, const drm_contact_plane *plane,
+                        const float *radius, const drm_joint_springs *springs, const float *lower, const float *upper, int32_t flags,
+                        float *tau, float *force, float *moment, float *, void *) {
+    if (int rc = check_sweep_walk(lw)) return rc;
+    if (!q || !qd || !tau) return fail(DRM_ERR_INVALID, "q / qd / tau must not be NULL");
+    if (!plane) return fail(DRM_ERR_INVALID, "drm_contact_torques needs a plane");
+    ContactArgs a;
+    if (int rc = contact_check(lw, B, T, plane, radius, springs, lower, upper, a)) return rc;
+    const int n = lw->n_dofs;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        contact_host_rows(lw, a, q + b0 * n, qd + b0 * n, nullptr, rows, T, n, flags, true, tau + b0 * n,
+                          force ? force + b0 * T * 3 : nullptr, moment ? moment + b0 * T * 3 : nullptr);
+    });
+    return DRM_OK;
+}
+
+int drm_contact_rollout(const drm_walk *dw, const drm_walk *lw, const float *q0, const float *qd0, const float *tau, int64_t B, int32_t T,
+                        float dt, int32_t flags, int32_t TL, const drm_contact_plane *plane, const float *radius,
+                        const drm_joint_springs *springs, const float *lower, const float *upper, float *q_traj, float *qd_traj,
+                        float *qdd_traj, float *, void *) {
+    if (int rc = check_walk(dw)) return rc;
+    if (!q0 || !qd0 || !tau || !q_traj || !qd_traj) return fail(DRM_ERR_INVALID, "q0 / qd0 / tau / q_traj / qd_traj must not be NULL");
+    if (T < 1) return fail(DRM_ERR_INVALID, "a rollout takes at least one step (T = %ld)", (long)T);
+    if (!(dt > 0.0f) || !std::isfinite(dt)) return fail(DRM_ERR_INVALID, "dt must be finite and positive");
+    ContactArgs a;
+    if (int rc = contact_check(lw, B, TL, plane, radius, springs, lower, upper, a)) return rc;
+    if (plane && lw->n_dofs != dw->n_dofs) return fail(DRM_ERR_INVALID, "the two walks are not of one robot");
+    const int n = dw->n_dofs, fd_flags = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
+    const bool expl = (flags & DRM_ROLLOUT_EXPLICIT_EULER) != 0;
+    const int64_t slab = B * n;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        std::vector<float> acc(qdd_traj ? 0 : (size_t)rows * n), total((size_t)rows * n);
+        for (int t = 0; t < T; ++t) {
+            const int64_t off = (int64_t)t * slab + b0 * n;
+            const float *qi = t ? q_traj + off - slab : q0 + b0 * n, *qdi = t ? qd_traj + off - slab : qd0 + b0 * n;
+            float *ac = qdd_traj ? qdd_traj + off : acc.data();
+            contact_host_rows(lw, a, qi, qdi, tau + off, rows, TL, n, flags, false, total.data(), nullptr, nullptr);
+            fd_loop(dw, qi, qdi, total.data(), rows, fd_flags, ac);
+            for (int64_t i = 0; i < rows * n; ++i) {
+                float x = qi[i], v = qdi[i];
+                drm::rollout_step(x, v, ac[i], dt, expl);
+                q_traj[off + i] = x;
+                qd_traj[off + i] = v;
+            }
+        }
+    });
     return DRM_OK;
 }
 

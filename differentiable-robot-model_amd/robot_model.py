@@ -166,6 +166,64 @@ class LinkMotion(NamedTuple):
     angular_acceleration: Optional[torch.Tensor]    # [B, L, 3] d/dt angular_velocity; None when qdd is None
 
 
+class PlaneContact:
+    """Penalty contact of spheres on the links with the plane {x : normal . x = offset} (csrc/drm_contact.hpp): a spring-damper along
+    the normal that never pulls, f_n = max(0, stiffness depth - damping v_n) while depth > 0, and regularised Coulomb friction
+    f_t = -min(friction_slope, friction f_n / |v_t|) v_t (viscous with slope ``friction_slope``, capped at ``friction`` f_n).
+    ``normal`` is normalised in float64.  ``radius``: one float for every link, or one value per entry of the call's ``link_names``;
+    the sphere is centred at the link origin and its lowest point is the contact point."""
+
+    def __init__(self, normal=(0.0, 0.0, 1.0), offset=0.0, *, stiffness, damping, friction=0.0, friction_slope=0.0, radius=0.0):
+        n = [float(x) for x in normal]
+        if len(n) != 3 or not all(math.isfinite(x) for x in n):
+            raise ValueError("normal must be three finite numbers (got %r)" % (normal,))
+        length = math.sqrt(sum(x * x for x in n))
+        if not length > 0.0:
+            raise ValueError("normal must not be zero")
+        self.normal = tuple(x / length for x in n)
+        self.offset = float(offset)
+        if not math.isfinite(self.offset):
+            raise ValueError("offset must be finite (got %r)" % (offset,))
+        for name, v in (("stiffness", stiffness), ("damping", damping), ("friction", friction), ("friction_slope", friction_slope)):
+            v = float(v)
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
+            setattr(self, name, v)
+        radii = [float(radius)] if isinstance(radius, (int, float)) else [float(r) for r in radius]
+        if not all(math.isfinite(r) and r >= 0.0 for r in radii):
+            raise ValueError("radius must be finite and >= 0 (got %r)" % (radius,))
+        self.radius = radii[0] if isinstance(radius, (int, float)) else tuple(radii)
+
+    def _plane(self):
+        return (self.normal, self.offset, self.stiffness, self.damping, self.friction, self.friction_slope)
+
+
+class JointLimitSprings:
+    """Spring-dampers at the joint limits (get_joint_limits(); a continuous joint is free): below the lower bound
+    tau = stiffness (lower - q) - damping qd, above the upper bound tau = -stiffness (q - upper) - damping qd, zero in between."""
+
+    def __init__(self, stiffness, damping=0.0):
+        self.stiffness, self.damping = float(stiffness), float(damping)
+        for name in ("stiffness", "damping"):
+            v = getattr(self, name)
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
+
+
+class ContactTorques(NamedTuple):
+    """What DifferentiableRobotModel.compute_contact_torques returns (no autograd history): world axes, at the link origins."""
+    tau: torch.Tensor                   # [B, n] sum_l lin_jac_l^T force_l + ang_jac_l^T moment_l, plus the joint-limit springs
+    force: torch.Tensor                 # [B, L, 3] the plane's force on each named link
+    moment: torch.Tensor                # [B, L, 3] its moment about the link origin
+
+
+class ContactRollout(NamedTuple):
+    """What DifferentiableRobotModel.compute_contact_rollout returns (no autograd history)."""
+    q: torch.Tensor                     # [T, B, n] the positions after steps 1 .. T
+    qd: torch.Tensor                    # [T, B, n] the velocities after steps 1 .. T
+    qdd: Optional[torch.Tensor]         # [T, B, n] the acceleration OF step t (at the state before it); None unless asked for
+
+
 class DifferentiableRobotModel(torch.nn.Module):
     """Batched FK / geometric Jacobian / RNEA on MI355X behind the reference API."""
 
@@ -2006,6 +2064,117 @@ class DifferentiableRobotModel(torch.nn.Module):
                 tau = backend.external_torques(dw.program, ops_f, dw.ops_i, q.detach(), f.detach() if f is not None else None,
                                                m.detach() if m is not None else None, T, self._n_dofs, composed=bool(_composed))
         return tau[0] if unbatched else tau
+
+    # ------------------------------------------------------------------ plane contact and joint-limit springs
+    def _contact_plan(self, contact, link_names, joint_limits):
+        """(links walk or None, T, sel, identity, plane tuple or None, radius [T] on the device or None, springs tuple or None)"""
+        if contact is not None and not isinstance(contact, PlaneContact):
+            raise TypeError("contact must be a PlaneContact (or None)")
+        if joint_limits is not None and not isinstance(joint_limits, JointLimitSprings):
+            raise TypeError("joint_limits must be a JointLimitSprings (or None)")
+        lw = sel = plane = radius = springs = None
+        T, identity = 0, True
+        if contact is not None:
+            lw, T, sel, identity = self._links_plan(link_names)
+            plane = contact._plane()
+            per_entry = contact.radius
+            if isinstance(per_entry, tuple):
+                if len(per_entry) != int(sel.numel()):
+                    raise ValueError("radius has %d values for %d link names" % (len(per_entry), int(sel.numel())))
+            if per_entry != 0.0:
+                key = (None if link_names is None else tuple(link_names), per_entry)
+                cache = self.__dict__.setdefault("_contact_radii", {})
+                radius = cache.get(key)
+                if radius is None:
+                    slots = [None] * T
+                    for pos, s in enumerate(sel.tolist()):
+                        r = per_entry[pos] if isinstance(per_entry, tuple) else per_entry
+                        if s < T:           # (the root never touches)
+                            if slots[s] is not None and slots[s] != r:
+                                raise ValueError("a link named twice has two different radii")
+                            slots[s] = r
+                    radius = cache[key] = torch.tensor(slots, dtype=torch.float32, device=self._device)
+        if joint_limits is not None:
+            lower, upper = self._joint_bounds()
+            springs = (joint_limits.stiffness, joint_limits.damping, lower, upper)
+        return lw, T, sel, identity, plane, radius, springs
+
+    def _refuse_grad(self, what, **tensors):
+        if torch.is_grad_enabled():
+            for name, t in tensors.items():
+                if t is not None and t.requires_grad:
+                    raise ValueError("%s is forward only: it has no gradient with respect to %s (pass %s.detach())" % (what, name, name))
+
+    def compute_contact_torques(self, q: torch.Tensor, qd: torch.Tensor, contact: PlaneContact, link_names: Optional[List[str]] = None,
+                                joint_limits: Optional[JointLimitSprings] = None, *, _composed: bool = False) -> ContactTorques:
+        """The joint torques of a plane's penalty contact with spheres on the named links (None: every link in get_link_names()
+        order) at q, qd [B, n], plus those of joint-limit springs when ``joint_limits`` is given, and the wrenches themselves:
+            tau     [B, n]     sum_l lin_jac_l^T force_l + ang_jac_l^T moment_l (+ tau_lim)
+            force   [B, L, 3]  the plane's force on link l, world axes       moment  [B, L, 3]  its moment about the link origin
+        The law is PlaneContact's; ``link_names`` is handled as in compute_link_motion (any order, repeats, the root — which never
+        touches and gets zeros).  ONE kernel launch for all 8 links of a 7-DoF arm on full 64-row tiles (csrc/drm_contact.hip: one
+        sweep outwards with velocities, the law per link, one sweep inwards, all in registers); every other robot and link set
+        composes the link-motion launch, one element-wise law kernel, the external-torques launch and one add.  Forward only: a q
+        or qd that requires grad raises ValueError, and the results carry no autograd history (the current values of learnable
+        links are used).  A row whose q or qd is not finite returns NaN and changes no bit of any other row."""
+        if contact is None:
+            raise ValueError("compute_contact_torques needs a PlaneContact")
+        unbatched, q, (qd,) = self._links_args(q, [(qd, "qd")], (self._n_dofs,))
+        assert qd is not None, "qd must be given"
+        self._refuse_grad("compute_contact_torques", q=q, qd=qd)
+        self._require_device()
+        with torch.no_grad():
+            lw, T, sel, identity, plane, radius, springs = self._contact_plan(contact, link_names, joint_limits)
+            tau, force, moment = backend.contact_torques(lw.program, self._ops_f(lw).detach(), lw.ops_i, q.detach(), qd.detach(), T,
+                                                         self._n_dofs, plane, radius, springs, composed=bool(_composed))
+            force, moment = self._links_gather(force, sel, identity), self._links_gather(moment, sel, identity)
+        return ContactTorques(*[x[0] if unbatched else x for x in (tau, force, moment)])
+
+    def compute_contact_rollout(self, q0: torch.Tensor, qd0: torch.Tensor, tau: torch.Tensor, dt: float,
+                                contact: Optional[PlaneContact], link_names: Optional[List[str]] = None,
+                                joint_limits: Optional[JointLimitSprings] = None, integrator: str = "semi_implicit_euler",
+                                include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False,
+                                return_acceleration: bool = False, *, _composed: bool = False) -> ContactRollout:
+        """compute_forward_dynamics_rollout with contact: step t computes
+            qdd_t = compute_forward_dynamics(q_t, qd_t, tau[t] + tau_ext(q_t, qd_t) + tau_lim(q_t, qd_t), include_gravity, use_damping)
+        with tau_ext, tau_lim compute_contact_torques' at the state of the step, then the integrator's update.  Shapes, the
+        time-major tau [T, B, n], the integrators and the unbatched form are compute_forward_dynamics_rollout's; ``qdd`` [T, B, n]
+        (the acceleration of each step) comes back with ``return_acceleration``.  ONE launch for a 7-DoF arm with all of its 8
+        links in contact, on full 64-row tiles with B n a multiple of 4 (csrc/drm_contact.hip: the state stays in registers across
+        the steps); every other case composes, per step, the contact torques, one add, the forward dynamics and the integrator on
+        the caller's stream.  ``contact=None`` needs ``joint_limits`` (the plain rollout exists for neither).  Forward only: a q0,
+        qd0 or tau that requires grad raises ValueError; the results carry no autograd history.  A row with a non-finite q0, qd0 or
+        tau gets non-finite results from that step on and changes no bit of any other row."""
+        if integrator not in self.ROLLOUT_INTEGRATORS:
+            raise ValueError("integrator must be one of %s (got %r)" % (self.ROLLOUT_INTEGRATORS, integrator))
+        if contact is None and joint_limits is None:
+            raise ValueError("neither contact nor joint_limits: compute_forward_dynamics_rollout is the plain rollout")
+        for name, t in (("q0", q0), ("qd0", qd0), ("tau", tau)):
+            assert type(t) is torch.Tensor, "%s must be a tensor" % name
+            assert t.device.type == self._device.type, f"Input argument of different device as module: {t}"
+        assert q0.ndim in [1, 2], "Input tensors must have ndim of 1 or 2."
+        assert qd0.shape == q0.shape, "Batch size mismatch between input tensors."
+        assert tau.ndim == q0.ndim + 1, "tau must be [T, B, n] ([T, n] for unbatched q0 / qd0)"
+        assert tau.shape[1:-1] == q0.shape[:-1], "Batch size mismatch between input tensors."
+        assert q0.shape[-1] == self._n_dofs and tau.shape[-1] == self._n_dofs
+        dt = float(dt)
+        if tau.shape[0] < 1:
+            raise ValueError("a rollout takes at least one step (tau has T = 0)")
+        if not (math.isfinite(dt) and dt > 0):
+            raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+        self._refuse_grad("compute_contact_rollout", q0=q0, qd0=qd0, tau=tau)
+        single = q0.ndim == 1
+        if single:
+            q0, qd0, tau = q0.unsqueeze(0), qd0.unsqueeze(0), tau.unsqueeze(1)
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            lw, T, _, _, plane, radius, springs = self._contact_plan(contact, link_names, joint_limits)
+            links = (lw.program, self._ops_f(lw).detach(), lw.ops_i) if lw is not None else None
+            out = backend.contact_rollout((dw.program, self._ops_f(dw).detach(), dw.ops_i), links, q0.detach(), qd0.detach(), tau.detach(),
+                                          dt, bool(include_gravity), bool(use_damping), integrator == "euler", T, self._n_dofs, plane,
+                                          radius, springs, want_qdd=bool(return_acceleration), composed=bool(_composed))
+        return ContactRollout(*[x[:, 0] if (single and x is not None) else x for x in out])
 
     def compute_inverse_dynamics_derivatives(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor,
                                              include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False, *,

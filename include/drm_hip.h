@@ -711,6 +711,51 @@ int drm_external_torques(const drm_walk *walk, const float *q, const float *forc
                          int32_t flags, float *tau, float *scratch, void *stream);
 
 /*
+ * Contact: spheres on the links against ONE plane (a penalty spring-damper with regularised Coulomb friction) and spring-dampers at the
+ * joint limits, as joint torques of one state (drm_contact_torques) and inside a rollout (drm_contact_rollout), where they depend on
+ * the state of every step and so cannot be handed to drm_forward_dynamics_rollout in advance.  The law (csrc/drm_contact.hpp), with
+ * p, v, w drm_link_motion's origin, linear and angular velocity of a contact link, rl its radius, n the unit normal (`normal` is
+ * normalised in double by the call), d = offset, k = stiffness, c = damping, mu = friction, c_t = friction_slope:
+ *   r = -rl n     depth = rl - (n.p - d)     v_c = v + w x r     v_n = n.v_c     v_t = v_c - v_n n
+ *   f_n = max(0, k depth - c v_n) if depth > 0, else 0          f_t = -min(c_t, mu f_n / |v_t|) v_t  (0 when mu, c_t, f_n or |v_t| is 0)
+ *   force = f_n n + f_t     moment = r x force     tau_ext = sum_t lin_jac_t^T force_t + ang_jac_t^T moment_t
+ *   q_j < lower_j:  tau_lim_j = k_l (lower_j - q_j) - c_l qd_j;   q_j > upper_j:  tau_lim_j = -k_l (q_j - upper_j) - c_l qd_j;   else 0
+ *   drm_contact_torques   tau [B, n] = tau_ext + tau_lim; force, moment [B, n_targets, 3] (either may be NULL: not stored)
+ *   drm_contact_rollout   drm_forward_dynamics_rollout with qdd_t = FD(q_t, qd_t, tau[t] + tau_ext(q_t, qd_t) + tau_lim(q_t, qd_t))
+ * `links_walk` is the many-target FK walk drm_link_motion takes and its n_targets the contact links; `dyn_walk` the dynamics walk of
+ * the same robot.  `plane` NULL: no contact (then springs must be given).  `radius`: DEVICE pointer to n_targets floats, or NULL = 0.
+ * `springs` NULL: no joint-limit springs; else lower / upper are DEVICE pointers to n floats (-inf / +inf: a free DoF).  flags:
+ * DRM_RNEA_GRAVITY, DRM_RNEA_DAMPING, DRM_ROLLOUT_EXPLICIT_EULER with drm_forward_dynamics_rollout's meaning, DRM_LINKS_COMPOSED.
+ * A links_walk that drm_link_motion runs fused (7-DoF arm chain of 8 ops, all targets in walk order; for the rollout also a dyn_walk
+ * that drm_forward_dynamics_rollout's arm kernel takes), full 64-row tiles, 16-byte aligned pointers and tables (rollout: slabs too,
+ * B n % 4 == 0): ONE launch, one wavefront per tile, one row per lane, state in registers across the steps.  Everything else is
+ * composed on the caller's stream out of the one scratch: drm_link_motion -> one element-wise law kernel -> drm_external_torques ->
+ * one add of the springs (and of tau[t]); per rollout step followed by drm_forward_dynamics and the integrator kernel.
+ * A row of drm_contact_torques with a q or qd that is not finite (|q| beyond 1e5) gets NaN in every output; a row of a rollout with a
+ * non-finite q0, qd0 or tau gets non-finite outputs from that step on.  Neither changes a bit of any other row.
+ * DRM_ERR_INVALID: a NULL required pointer, T < 1, a dt that is not finite and positive, a plane or spring parameter that is not
+ * finite or is negative, a zero normal, B < 0, neither plane nor springs; B == 0 returns DRM_OK.  Asynchronous on `stream`, no
+ * allocation, never a host synchronisation.
+ */
+typedef struct drm_contact_plane {
+    float normal[3], offset, stiffness, damping, friction, friction_slope;
+} drm_contact_plane;
+typedef struct drm_joint_springs {
+    float stiffness, damping;
+} drm_joint_springs;
+int64_t drm_contact_torques_scratch_floats(const drm_walk *links_walk, int64_t B);
+int64_t drm_contact_torques_scratch_floats_aligned(const drm_walk *links_walk, int64_t B);
+int64_t drm_contact_rollout_scratch_floats(const drm_walk *dyn_walk, const drm_walk *links_walk, int64_t B);
+int64_t drm_contact_rollout_scratch_floats_aligned(const drm_walk *dyn_walk, const drm_walk *links_walk, int64_t B);
+int drm_contact_torques(const drm_walk *links_walk, const float *q, const float *qd, int64_t B, int32_t n_targets,
+                        const drm_contact_plane *plane, const float *radius, const drm_joint_springs *springs, const float *lower,
+                        const float *upper, int32_t flags, float *tau, float *force, float *moment, float *scratch, void *stream);
+int drm_contact_rollout(const drm_walk *dyn_walk, const drm_walk *links_walk, const float *q0, const float *qd0, const float *tau,
+                        int64_t B, int32_t T, float dt, int32_t flags, int32_t n_targets, const drm_contact_plane *plane,
+                        const float *radius, const drm_joint_springs *springs, const float *lower, const float *upper, float *q_traj,
+                        float *qd_traj, float *qdd_traj, float *scratch, void *stream);
+
+/*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
  * compute_forward_kinematics' outputs is back-propagated to q and to learnable `trans` / `rot_angles`
  * (robot_model.py:139-195, 223-248, 669-713; examples/learn_kinematics_of_iiwa.py:25-61).
