@@ -10,7 +10,7 @@ here one node per public method:
     _MassMatrix       compute_lagrangian_inertia_matrix                               drm_crba / drm_rnea_backward per column
     _ForwardDynamics  compute_forward_dynamics (implicit differentiation)             drm_forward_dynamics / drm_rnea_backward
     _Energy           compute_energy (T, V and their gradients from ONE launch; first order only)          drm_energy
-    _LinkAdjoint      compute_link_velocities / compute_external_torques (each the other's backward)       drm_link_motion, drm_external_torques
+    _LinkAdjoint      compute_link_velocities / compute_external_torques (each the other's backward)       drm_link_motion, drm_external_torques, drm_link_power_dq
     _FirstOrderOnly   marks the gradients of _FkMse computed under create_graph=True (differentiating through them raises)
     _GradLaunch       a first-order gradient launch as a differentiable node (create_graph=True: second derivatives with respect to
                       q / qd / qdd / f, the output cotangents and — round 6 — the walk's table, i.e. the learnable link parameters)
@@ -733,13 +733,25 @@ class _LinkAdjoint(torch.autograd.Function):
         torques=False   (lin_vel, ang_vel) [B, T, 3] = J qd            backward: grad_qd = J^T (g_lin, g_ang) — the torques launch
         torques=True    tau [B, n] = J^T (force, torque)               backward: (grad_force, grad_torque) = J g_tau — the motion launch
     so each gradient IS the other method's forward on the same arguments, to the bit.  First order only (once_differentiable): a second
-    backward through it raises.  No gradient with respect to q (it needs the kinematic Hessian): the callers refuse a q that requires
-    grad.  The walk's table is a constant of the node: no history flows to learnable link parameters."""
+    backward through it raises.  The walk's table is a constant of the node: no history flows to learnable link parameters.
+
+    ``diff_q`` (the callers' differentiable_q=True): the node also has a gradient with respect to q.  Both directions are the two
+    sides of one scalar, the power S = (force, torque) . J qd, so both q-gradients are dS/dq of ONE more launch (backend.link_power_dq;
+    no kinematic Hessian):
+        torques=False   grad_q = dS/dq at (qd, g_lin, g_ang); grad_qd, when it is wanted too, is the tau of the same launch
+        torques=True    grad_q = dS/dq at (g_tau, force, torque)
+    Without it the callers refuse a q that requires grad."""
 
     @staticmethod
-    def forward(ctx, torques, q, a, b, prog, ops_f, ops_i, n_targets, n_dofs, composed):
+    def forward(ctx, torques, q, a, b, prog, ops_f, ops_i, n_targets, n_dofs, composed, diff_q=False):
+        ctx.q_dtype = q.dtype
         q = q.detach()
-        ctx.save_for_backward(q)
+        if diff_q:
+            ctx.save_for_backward(q, *[t.detach() for t in (a, b) if t is not None])
+            ctx.given = (a is not None, b is not None)
+        else:
+            ctx.save_for_backward(q)
+        ctx.diff_q = bool(diff_q)
         ctx.call = (prog, ops_f, ops_i, n_targets, n_dofs, composed)
         ctx.torques = torques
         ctx.dtypes = (a.dtype if a is not None else None, b.dtype if b is not None else None)
@@ -753,15 +765,26 @@ class _LinkAdjoint(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
-        (q,) = ctx.saved_tensors
+        q = ctx.saved_tensors[0]
         prog, ops_f, ops_i, n_targets, n_dofs, composed = ctx.call
-        ga = gb = None
+        need_q = ctx.diff_q and ctx.needs_input_grad[1]
+        gq = ga = gb = None
         if ctx.torques:
             want = tuple(name for name, need in zip(("linear_velocity", "angular_velocity"), ctx.needs_input_grad[2:4]) if need)
             if want:
                 out = backend.link_motion(prog, ops_f, ops_i, q, grads[0], None, n_targets, n_dofs, want=want, composed=composed)
                 ga = out[1].to(ctx.dtypes[0]) if out[1] is not None else None
                 gb = out[2].to(ctx.dtypes[1]) if out[2] is not None else None
+            if need_q:
+                rest = list(ctx.saved_tensors[1:])
+                f = rest.pop(0) if ctx.given[0] else None
+                m = rest.pop(0) if ctx.given[1] else None
+                gq = backend.link_power_dq(prog, ops_f, ops_i, q, grads[0], f, m, n_targets, n_dofs, composed=composed)[0].to(ctx.q_dtype)
+        elif need_q:
+            gq, tau = backend.link_power_dq(prog, ops_f, ops_i, q, ctx.saved_tensors[1], grads[0], grads[1], n_targets, n_dofs,
+                                            want_tau=ctx.needs_input_grad[2], composed=composed)
+            gq = gq.to(ctx.q_dtype)
+            ga = tau.to(ctx.dtypes[0]) if tau is not None else None
         elif ctx.needs_input_grad[2]:
             ga = backend.external_torques(prog, ops_f, ops_i, q, grads[0], grads[1], n_targets, n_dofs, composed=composed).to(ctx.dtypes[0])
-        return None, None, ga, gb, None, None, None, None, None, None
+        return None, gq, ga, gb, None, None, None, None, None, None, None

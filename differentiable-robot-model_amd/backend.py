@@ -114,6 +114,7 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_energy", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
            "drm_link_motion", "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
            "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
+           "drm_link_power_dq", "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
            "drm_contact_torques", "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
            "drm_contact_rollout", "drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned")
 
@@ -218,6 +219,7 @@ def load_library(path: str = None, kind: str = "cuda"):
                      "drm_rnea_derivatives_scratch_floats_aligned", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
                      "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
                      "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
+                     "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
                      "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
@@ -248,6 +250,8 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_link_motion.argtypes = [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         lib.drm_external_torques.restype = ctypes.c_int
         lib.drm_external_torques.argtypes = [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
+        lib.drm_link_power_dq.restype = ctypes.c_int
+        lib.drm_link_power_dq.argtypes = [wp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]
         lib.drm_special_load.restype = ctypes.c_int
         lib.drm_special_load.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.drm_fk_mse.restype = ctypes.c_int
@@ -1226,6 +1230,41 @@ def external_torques(prog: WalkProgram, ops_f, ops_i, q, force, torque, n_target
         _check(lib.drm_external_torques(ctypes.byref(walk), q.data_ptr(), ptr(force), ptr(torque), B, n_targets,
                                         LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(scratch), _stream(q.device)), lib)
     return tau
+
+
+def link_power_dq(prog: WalkProgram, ops_f, ops_i, q, qd, force, torque, n_targets: int, n_dofs: int, want_tau: bool = False,
+                  composed: bool = False):
+    """(dq [B, n], tau [B, n] or None): dq = dS/dq of the power S = sum_t force_t . lin_vel_t + torque_t . ang_vel_t = tau . qd of
+    wrenches [B, T, 3] on the T targets of a many-target FK walk, with qd and the wrenches held fixed, in one launch
+    (include/drm_hip.h drm_link_power_dq): the q-gradient of link_motion's velocities under the cotangents (force, torque) and of
+    external_torques under the cotangent qd.  ``want_tau``: external_torques' result on the same arguments, to the bit, from the same
+    launch.  Either of ``force`` / ``torque`` may be None (zero), not both.  ``composed``: as for link_motion."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B:
+        raise ValueError("q / qd batch sizes differ")
+    if force is None and torque is None:
+        raise ValueError("force and torque are both None")
+
+    def wrench(t, name):
+        if t is None:
+            return None
+        if t.ndim != 3 or tuple(t.shape) != (B, n_targets, 3):
+            raise ValueError("%s must be [%d, %d, 3], got %s" % (name, B, n_targets, tuple(t.shape)))
+        return _dev_f32(t.reshape(B, n_targets * 3), name, n_targets * 3)
+    force, torque = wrench(force, "force"), wrench(torque, "torque")
+    dq, tau = (_outputs(q.device, *[(B, n_dofs)] * (2 if want_tau else 1)) + [None])[:2]
+    if B == 0:
+        return dq, tau
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _scratch(lib, "drm_link_power_dq", (walk,), B, composed, q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_link_power_dq(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), ptr(force), ptr(torque), B, n_targets,
+                                     LINKS_COMPOSED if composed else 0, dq.data_ptr(), ptr(tau), ptr(scratch), _stream(q.device)), lib)
+    return dq, tau
 
 
 def _contact_structs(plane, radius, springs, n_targets: int, n_dofs: int, device):

@@ -430,6 +430,49 @@ void link_torques_host_rows(const drm_walk *w, const float *q, const float *forc
             [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, wrench, jout);
     }
 }
+// drm_link_power_dq, rows [b0, b0 + rows)
+void link_power_dq_host_rows(const drm_walk *w, const float *q, const float *qd, const float *force, const float *torque, int64_t b0,
+                             int64_t rows, int T, int flags, float *dq, float *tau) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    HostRecords<drm::LINKS_DQ_REC_FLOATS> rec(n_ops); HostRecords<drm::LINKS_SLOT_FLOATS> slots(n_slots);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const bool chain = links_chain_walk(w, T, flags);
+    auto row = [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; };
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = qd + b * n;
+        const float *fr = force ? force + b * T * 3 : nullptr, *mr = torque ? torque + b * T * 3 : nullptr;
+        float *gr = dq + b * n, *tr = tau ? tau + b * n : nullptr;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(qr[d], qdr[d]);
+        for (int d = 0; d < n; ++d) {
+            gr[d] = bad ? nan : 0.0f;
+            if (tr) tr[d] = bad ? nan : 0.0f;
+        }
+        auto wrench = [&](int t, float *f, float *m) {
+            for (int i = 0; i < 3; ++i) {
+                f[i] = (fr && t < T) ? fr[3 * t + i] : 0.0f;
+                m[i] = (mr && t < T) ? mr[3 * t + i] : 0.0f;
+            }
+        };
+        auto jout = [&](int j, float g, float t) {
+            if (j >= n) return;
+            gr[j] = bad ? nan : g;
+            if (tr) tr[j] = bad ? nan : t;
+        };
+        if (chain) {
+            float qv[7], qdv[7], cs[7], sn[7];
+            for (int d = 0; d < 7; ++d) { qv[d] = bad ? 0.0f : qr[d]; qdv[d] = bad ? 0.0f : qdr[d]; }
+            drm::chain_trig<7>(qv, cs, sn);
+            drm::link_chain_power_dq<8, 7>(row, cs, sn, qdv, wrench, jout);
+            continue;
+        }
+        drm::link_power_dq_walk(
+            n_ops, n_slots, ctl, row, [&](int d, float &a, float &v) { a = bad ? 0.0f : qr[d]; v = bad ? 0.0f : qdr[d]; },
+            [&](int k, const float *x) { rec.put(k, x); }, [&](int k, float *x) { rec.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, wrench, jout);
+    }
+}
 // what drm_contact_torques and drm_contact_rollout ask of their contact arguments (drm_contact.hip contact_check)
 struct ContactArgs {
     drm::ContactPlane pl;
@@ -826,6 +869,21 @@ int drm_external_torques(const drm_walk *w, const float *q, const float *force, 
     if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
     if (!tau) return fail(DRM_ERR_INVALID, "tau must not be NULL");
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { link_torques_host_rows(w, q, force, torque, b0, rows, T, flags, tau); });
+    return DRM_OK;
+}
+
+int64_t drm_link_power_dq_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_link_power_dq_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+int drm_link_power_dq(const drm_walk *w, const float *q, const float *qd, const float *force, const float *torque, int64_t B, int32_t T,
+                      int32_t flags, float *dq, float *tau, float *, void *) {
+    if (int rc = check_sweep_walk(w)) return rc;
+    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
+    if (!qd) return fail(DRM_ERR_INVALID, "qd must not be NULL");
+    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
+    if (!dq) return fail(DRM_ERR_INVALID, "dq must not be NULL");
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { link_power_dq_host_rows(w, q, qd, force, torque, b0, rows, T, flags, dq, tau); });
     return DRM_OK;
 }
 

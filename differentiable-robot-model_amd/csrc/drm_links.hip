@@ -17,8 +17,14 @@
 //                             tail of an arm launch, misaligned pointers, DRM_LINKS_COMPOSED: one lane per row, loops over the ops
 //                             (drm_links.hpp link_motion_walk / link_torques_walk).  A row keeps 24 floats per branch point
 //                             (motion) or 12 floats per op and 24 per branch point (torques), placed by drm_rows.hpp.
+//   link_power_dq_arm_kernel, link_power_dq_rows_kernel
+//                             drm_link_power_dq, the q-gradient of both sweeps as dS/dq of the power S = sum_l f_l . v_l + m_l . w_l:
+//                             the torques kernels with the velocities carried outwards and one more free vector inwards
+//                             (drm_links.hpp link_chain_power_dq / link_power_dq_walk); tau, when asked for, is drm_external_torques'
+//                             to the bit.  Same dispatch, same tiles; the general kernel keeps 21 floats per op.
 //
-// Per row, fused, T = 8: motion 84 B in (q, qd, qdd), up to 5 x 96 = 480 B out; torques 28 + 2 x 96 = 220 B in, 28 B out.
+// Per row, fused, T = 8: motion 84 B in (q, qd, qdd), up to 5 x 96 = 480 B out; torques 28 + 2 x 96 = 220 B in, 28 B out; power
+// gradient 56 + 2 x 96 = 248 B in, 28 B (dq) or 56 B (dq and tau) out.
 #include <math.h>
 
 #include "drm_common.hpp"
@@ -33,6 +39,7 @@ constexpr int LINKS_LDS_BYTES = 32 * 1024; // per-row state of the general kerne
 // (a walk without branch points still gets one slot's worth: a plan of zero floats would read as "the state lives in the scratch")
 static inline int motion_state_floats(const drm_walk *w) { return LINKS_SLOT_FLOATS * (w->n_slots > 0 ? w->n_slots : 1); }
 static inline int torques_state_floats(const drm_walk *w) { return LINKS_REC_FLOATS * w->n_ops + LINKS_SLOT_FLOATS * w->n_slots; }
+static inline int power_dq_state_floats(const drm_walk *w) { return LINKS_DQ_REC_FLOATS * w->n_ops + LINKS_SLOT_FLOATS * w->n_slots; }
 
 // floor(w / S) == umulhi(w, tile_magic(S)) for w S < 2^32 (drm_common.hpp div_magic, as a constant)
 constexpr uint32_t tile_magic(int S) { return (uint32_t)((((uint64_t)1 << 32) + (uint64_t)S - 1) / (uint64_t)S); }
@@ -253,6 +260,120 @@ __global__ void __launch_bounds__(WAVE)
     }
 }
 
+// drm_link_power_dq, fused: link_torques_arm_kernel's tiles and LDS image, with the [64, 7] tiles of q and qd coming in through LDS in
+// 16-byte loads as well.  The origins, velocities and angular velocities of the 8 links and the axes of the 7 joints stay in registers
+// from the sweep out; the wrenches are read out of their LDS tiles on the way in (nothing else writes those), and the [64, 7] tiles of
+// the gradient and of the torques leave through the buffers q and qd came in by.  tau NULL (wave-uniform): not stored.
+template <int CAP, int NJ, int LINKS>
+__global__ void __launch_bounds__(WAVE)
+    link_power_dq_arm_kernel(const float *__restrict__ ops_f, const float *__restrict__ q, const float *__restrict__ qd,
+                             const float *__restrict__ force, const float *__restrict__ torque, int n_tiles, float *__restrict__ dq,
+                             float *__restrict__ tau) {
+    static_assert(NJ & 1, "odd row widths only (linear LDS image)");
+    static_assert(CAP * DRM_OPF_STRIDE == 4 * WAVE, "one float4 per lane copies the constant table");
+    constexpr int S = 3 * LINKS, SP = S | 1;
+    static_assert(!(S & 1) && !((WAVE * S) & 3), "even row widths (padded LDS image), whole 16-byte loads");
+    constexpr int C_FLOATS = CAP * DRM_OPF_STRIDE, T_FLOATS = round4(WAVE * SP), Q_FLOATS = round4(WAVE * NJ);
+    __shared__ __attribute__((aligned(16))) float smem[C_FLOATS + 2 * T_FLOATS + 2 * Q_FLOATS];
+    const int tile = (int)blockIdx.x;
+    if (tile >= n_tiles) return;
+    const unsigned lane = threadIdx.x & 63u;
+    float *lc = smem, *lf = smem + C_FLOATS, *lm = lf + T_FLOATS, *lq = lm + T_FLOATS, *lqd = lq + Q_FLOATS;
+    const int64_t b0 = (int64_t)tile * WAVE;
+
+    float4 cv = reinterpret_cast<const float4 *>(ops_f)[lane];
+    tile_load<NJ>(q + b0 * NJ, WAVE, NJ, 0u, lq, lane, true);
+    tile_load<NJ>(qd + b0 * NJ, WAVE, NJ, 0u, lqd, lane, true);
+    if (force) tile_load<S>(force + b0 * S, WAVE, S, tile_magic(S), lf, lane, false, true);
+    if (torque) tile_load<S>(torque + b0 * S, WAVE, S, tile_magic(S), lm, lane, false, true);
+    pin(cv);
+    reinterpret_cast<float4 *>(lc)[lane] = cv;
+    wave_lds_sync();
+    auto row = [&](int k) -> const float * { return lc + k * DRM_OPF_STRIDE; };
+
+    float qv[NJ], qdv[NJ];
+#pragma unroll
+    for (int d = 0; d < NJ; ++d) { qv[d] = lq[lane * NJ + d]; qdv[d] = lqd[lane * NJ + d]; }
+    wave_lds_sync(); // (the gradient and torque tiles below reuse lq and lqd)
+
+    bool bad = false;
+#pragma unroll
+    for (int d = 0; d < NJ; ++d) bad = bad || lag_bad_input(qv[d], qdv[d]);
+#pragma unroll
+    for (int d = 0; d < NJ; ++d) { qv[d] = bad ? 0.0f : qv[d]; qdv[d] = bad ? 0.0f : qdv[d]; }
+    const float nan = __builtin_nanf("");
+
+    float cs[NJ], sn[NJ];
+    chain_trig<NJ>(qv, cs, sn);
+    float *ldq = lq + lane * NJ, *ltau = lqd + lane * NJ;
+    const float *lfr = lf + lane * SP, *lmr = lm + lane * SP;
+    link_chain_power_dq<LINKS, NJ>(
+        row, cs, sn, qdv,
+        [&](int k, float *f, float *m) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { f[i] = force ? lfr[3 * k + i] : 0.0f; m[i] = torque ? lmr[3 * k + i] : 0.0f; }
+        },
+        [&](int j, float g, float t) {
+            ldq[j] = bad ? nan : g;
+            ltau[j] = bad ? nan : t;
+        });
+    wave_lds_sync();
+    tile_store<NJ>(dq + b0 * NJ, WAVE, NJ, 0u, lq, lane, true);
+    if (tau) tile_store<NJ>(tau + b0 * NJ, WAVE, NJ, 0u, lqd, lane, true);
+}
+
+template <bool IN_LDS>
+__global__ void __launch_bounds__(WAVE)
+    link_power_dq_rows_kernel(const float *__restrict__ ops_f, const int32_t *__restrict__ ops_i, int cap, int n_ops, int n_slots, int n, int T,
+                              const float *__restrict__ q, const float *__restrict__ qd, const float *__restrict__ force,
+                              const float *__restrict__ torque, int64_t B, int64_t n_tiles, float *__restrict__ dq, float *__restrict__ tau,
+                              float *__restrict__ scratch, int state_floats) {
+    const unsigned lane = threadIdx.x & 63u;
+    float *state = rows_state<IN_LDS>(scratch, state_floats);
+    const Records<LINKS_DQ_REC_FLOATS, WAVE> recs = {state};
+    const Records<LINKS_SLOT_FLOATS, WAVE> slots = {state + LINKS_DQ_REC_FLOATS * n_ops * WAVE};
+    const RowsCtl ctl(ops_i, cap);
+    const float nan = __builtin_nanf("");
+    auto row = [&](int k) -> const float * { return ops_f + k * DRM_OPF_STRIDE; };
+#pragma unroll 1
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t r = tile * WAVE + lane;
+        if (r >= B) continue;
+        const float *qr = q + r * n, *qdr = qd + r * n;
+        const float *fr = force ? force + r * T * 3 : nullptr, *mr = torque ? torque + r * T * 3 : nullptr;
+        float *gr = dq + r * n, *tr = tau ? tau + r * n : nullptr;
+        bool bad = false;
+#pragma unroll 1
+        for (int d = 0; d < n; ++d) bad = bad || lag_bad_input(qr[d], qdr[d]);
+        // (columns of DoFs that no target's chain crosses stay zero)
+#pragma unroll 1
+        for (int d = 0; d < n; ++d) {
+            gr[d] = bad ? nan : 0.0f;
+            if (tr) tr[d] = bad ? nan : 0.0f;
+        }
+        link_power_dq_walk(
+            n_ops, n_slots, ctl, row,
+            [&](int d, float &a, float &v) {
+                a = bad ? 0.0f : qr[d];
+                v = bad ? 0.0f : qdr[d];
+            },
+            [&](int k, const float *x) { recs.put(k, x); }, [&](int k, float *x) { recs.get(k, x); },
+            [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
+            [&](int t, float *f, float *m) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    f[i] = (fr && t < T) ? fr[3 * t + i] : 0.0f;
+                    m[i] = (mr && t < T) ? mr[3 * t + i] : 0.0f;
+                }
+            },
+            [&](int j, float g, float t) {
+                if (j >= n) return;
+                gr[j] = bad ? nan : g;
+                if (tr) tr[j] = bad ? nan : t;
+            });
+    }
+}
+
 // an arm7_walk of 8 ops whose every op is a target, slots in walk order: what the fused kernels are compiled for
 static inline bool links_fused(const drm_walk *w, int T, int64_t B, int flags, bool aligned) {
     return !(flags & DRM_LINKS_COMPOSED) && (w->shape & DRM_WALK_TARGETS_ORDERED) && w->n_ops == 8 && T == 8 && rows_fused(w, B, aligned);
@@ -283,6 +404,8 @@ extern "C" int64_t drm_external_torques_scratch_floats(const drm_walk *w, int64_
     return links_scratch(w, B, w ? torques_state_floats(w) : 0);
 }
 extern "C" int64_t drm_external_torques_scratch_floats_aligned(const drm_walk *w, int64_t B) { return drm_external_torques_scratch_floats(w, B); }
+extern "C" int64_t drm_link_power_dq_scratch_floats(const drm_walk *w, int64_t B) { return links_scratch(w, B, w ? power_dq_state_floats(w) : 0); }
+extern "C" int64_t drm_link_power_dq_scratch_floats_aligned(const drm_walk *w, int64_t B) { return drm_link_power_dq_scratch_floats(w, B); }
 
 extern "C" int drm_link_motion(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t n_targets,
                                int32_t flags, float *pos, float *lin_vel, float *ang_vel, float *lin_acc, float *ang_acc, float *scratch,
@@ -348,4 +471,32 @@ extern "C" int drm_external_torques(const drm_walk *w, const float *q, const flo
     return rows_launch(link_torques_rows_kernel<true>, link_torques_rows_kernel<false>, plan, scratch, "drm_external_torques_scratch_floats",
                        s, w->ops_f, w->ops_i, (int)w->capacity, (int)w->n_ops, (int)w->n_slots, n, T, q + lo * n,
                        force ? force + lo * T * 3 : nullptr, torque ? torque + lo * T * 3 : nullptr, rows, plan.tiles, tau + lo * n);
+}
+
+extern "C" int drm_link_power_dq(const drm_walk *w, const float *q, const float *qd, const float *force, const float *torque, int64_t B,
+                                 int32_t n_targets, int32_t flags, float *dq, float *tau, float *scratch, void *stream) {
+    int rc = links_check(w, q, B, n_targets);
+    if (rc) return rc;
+    if (!qd) return fail(DRM_ERR_INVALID, "qd must not be NULL");
+    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
+    if (!dq) return fail(DRM_ERR_INVALID, "dq must not be NULL");
+    if (B == 0) return DRM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int n = w->n_dofs, T = n_targets;
+    int64_t lo = 0;
+    if (links_fused(w, T, B, flags, aligned16(q, qd, force, torque, dq, tau))) {
+        const int n_tiles = (int)(B / WAVE);
+        hipLaunchKernelGGL((link_power_dq_arm_kernel<8, 7, 8>), dim3((unsigned)n_tiles), dim3(WAVE), 0, s, w->ops_f, q, qd, force, torque,
+                           n_tiles, dq, tau);
+        rc = launched();
+        if (rc) return rc;
+        lo = (int64_t)n_tiles * WAVE;
+        if (lo == B) return DRM_OK;
+    }
+    const int64_t rows = B - lo;
+    const RowsPlan plan = rows_plan(rows, power_dq_state_floats(w), LINKS_LDS_BYTES);
+    return rows_launch(link_power_dq_rows_kernel<true>, link_power_dq_rows_kernel<false>, plan, scratch, "drm_link_power_dq_scratch_floats", s,
+                       w->ops_f, w->ops_i, (int)w->capacity, (int)w->n_ops, (int)w->n_slots, n, T, q + lo * n, qd + lo * n,
+                       force ? force + lo * T * 3 : nullptr, torque ? torque + lo * T * 3 : nullptr, rows, plan.tiles, dq + lo * n,
+                       tau ? tau + lo * n : nullptr);
 }

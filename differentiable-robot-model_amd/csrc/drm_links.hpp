@@ -20,6 +20,7 @@
 //
 // v = lin_jac qd, w = ang_jac qd, a = d/dt v (gravity not included), al = d/dt w; tau = sum_l lin_jac_l^T f_l + ang_jac_l^T m_l.  The
 // two sweeps are adjoint: sum_l f_l . v_l + m_l . w_l == tau . qd for every qd, so each serves as the other's exact backward pass.
+// The q-gradient of that scalar (drm_link_power_dq) is the q-gradient of both: see link_joint_power_dq below.
 #pragma once
 #include "drm_lagrangian.hpp"
 
@@ -27,6 +28,7 @@ namespace drm {
 
 constexpr int LINKS_SLOT_FLOATS = 24; // motion: the state of a branch point (R, p, w, v, al, a) parked for its later children
 constexpr int LINKS_REC_FLOATS = 12;  // torques, per op: origin p, axis z, and the wrench (F, M) its children have handed up so far
+constexpr int LINKS_DQ_REC_FLOATS = 21; // power gradient, per op: p, z, v, w, and (F, M, A) its children have handed up so far
 
 struct LinkState {
     float R[9], p[3]; // world pose of the stored frame
@@ -290,6 +292,147 @@ DRM_HD void link_chain_torques(ROW row, const float (&cs)[NJ], const float (&sn)
 #pragma unroll
         for (int i = 0; i < 3; ++i) { F[i] += Fc[i]; M[i] += Mc[i]; }
         if (k < NJ) jout(k, link_joint_torque(z[k < NJ ? k : 0], F, M, false));
+        if (k > 0) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { Fc[i] = 0.0f; Mc[i] = 0.0f; }
+            link_wrench_up(p[k], p[k > 0 ? k - 1 : 0], F, M, Fc, Mc);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// include/drm_hip.h drm_link_power_dq: the q-gradient of the power of the wrenches,
+//   S(q; qd, F, M) = sum_l F_l . v_l + M_l . w_l = tau_ext(q; F, M) . qd,
+// with the rates and the wrenches held fixed.  It is the q-gradient of BOTH sweeps above: of the velocities with (F, M) := their
+// cotangents, of the torques with qd := theirs.  Turning joint j turns its sub-tree rigidly about (p_j, z_j): what the sub-tree's own
+// joints add to a velocity turns with it, what the joints before j add is the parent's velocity field read at a moved point.  With
+// F^S_j, M^S_j the sub-tree's wrench about p_j (the inward sweep of the torques) and one more FREE vector carried inwards,
+//   A_k = v_k x F_k + w_k x M_k + sum over children A_c                                 (no transport)
+//   revolute    dS/dq_j = z_j . (A_j - v_j x F^S_j) + (w_j x z_j) . M^S_j               (w_j x z_j == w_parent x z_j)
+//   prismatic   dS/dq_j = (w_j x z_j) . F^S_j
+//   fixed       transport only
+// so no kinematic Hessian is formed.  The inward sweep forms F^S, M^S by link_torques_walk's own operations in its own order: the
+// torques it hands out next to the gradient are drm_external_torques' to the bit.
+DRM_HD float link_joint_power_dq(const float *z, const float *v, const float *w, const float *F, const float *M, const float *A,
+                                 bool prismatic) {
+    float wz[3], vF[3];
+    lk_cross(w, z, wz);
+    lk_cross(v, F, vF);
+    const float t0 = A[0] - vF[0], t1 = A[1] - vF[1], t2 = A[2] - vF[2];
+    const float slide = lk_dot(wz[0], wz[1], wz[2], F[0], F[1], F[2]);
+    const float turn = __builtin_fmaf(z[2], t2, __builtin_fmaf(z[1], t1, __builtin_fmaf(z[0], t0, lk_dot(wz[0], wz[1], wz[2], M[0], M[1], M[2]))));
+    return prismatic ? slide : turn;
+}
+// A += v x f + w x m: the link's own term of the free vector
+DRM_HD void link_power_own(const float *v, const float *w, const float *f, const float *m, float *A) {
+    float vf[3], wm[3];
+    lk_cross(v, f, vf);
+    lk_cross(w, m, wm);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) A[i] += vf[i] + wm[i];
+}
+
+// ANY many-target FK walk, one row.  Outwards link_motion_walk's sweep with the velocities, leaving (p, z, v, w) and zero (F, M, A)
+// accumulators per op (LINKS_DQ_REC_FLOATS); inwards link_torques_walk's sweep with A beside the wrench.
+//   qf(d, q, qd)                       joint value and rate of DoF d
+//   rput / rget, sput / sget, wrench   as link_torques_walk's (records of LINKS_DQ_REC_FLOATS)
+//   jout(dof, dS/dq, tau)
+template <class CTL, class ROW, class QF, class RPUT, class RGET, class SPUT, class SGET, class WRENCH, class JOUT>
+DRM_HD void link_power_dq_walk(int n_ops, int n_slots, CTL ctl, ROW row, QF qf, RPUT rput, RGET rget, SPUT sput, SGET sget, WRENCH wrench,
+                               JOUT jout) {
+    float sl[LINKS_SLOT_FLOATS], rec[LINKS_DQ_REC_FLOATS];
+    {
+        LinkState cur;
+        link_state_root(cur);
+#pragma unroll 1
+        for (int k = 0; k < n_ops; ++k) {
+            int w0, w1;
+            ctl_words(ctl, k, w0, w1);
+            const OpCtl ct = decode_ctl(w0, w1);
+            float q = 0.0f, qd = 0.0f, c = 1.0f, s = 0.0f;
+            if (ct.dof >= 0) {
+                qf(ct.dof, q, qd);
+                if (!ct.prismatic) sincos_one(q, s, c);
+            }
+            if (ct.src == DRM_SRC_ROOT) {
+                link_state_root(cur);
+            } else if (ct.src >= 0 && ct.src < n_slots) {
+                sget(ct.src, sl);
+                link_state_from_floats(sl, cur);
+            }
+            const OpFT o = load_ft(row(k));
+            float J[9], t[3];
+            link_joint_transform(o, ct.dof >= 0, ct.prismatic, q, c, s, J, t);
+            link_step<true, false>(J, t, ct.dof >= 0, ct.prismatic, qd, 0.0f, cur);
+            if (ct.save >= 0 && ct.save < n_slots) {
+                link_state_to_floats(cur, sl);
+                sput(ct.save, sl);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                rec[i] = cur.p[i]; rec[3 + i] = cur.R[3 * i + 2]; rec[6 + i] = cur.v[i]; rec[9 + i] = cur.w[i];
+                rec[12 + i] = 0.0f; rec[15 + i] = 0.0f; rec[18 + i] = 0.0f;
+            }
+            rput(k, rec);
+        }
+    }
+#pragma unroll 1
+    for (int k = n_ops - 1; k >= 0; --k) {
+        int w0, w1;
+        ctl_words(ctl, k, w0, w1);
+        const OpCtl ct = decode_ctl(w0, w1);
+        rget(k, rec);
+        float F[3] = {rec[12], rec[13], rec[14]}, M[3] = {rec[15], rec[16], rec[17]}, A[3] = {rec[18], rec[19], rec[20]};
+        if (ct.out >= 0) {
+            float f[3], m[3];
+            wrench(ct.out, f, m);
+            link_power_own(rec + 6, rec + 9, f, m, A);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { F[i] += f[i]; M[i] += m[i]; }
+        }
+        if (ct.dof >= 0)
+            jout(ct.dof, link_joint_power_dq(rec + 3, rec + 6, rec + 9, F, M, A, ct.prismatic), link_joint_torque(rec + 3, F, M, ct.prismatic));
+        if (ct.parent >= 0 && ct.parent < k) {
+            float par[LINKS_DQ_REC_FLOATS];
+            rget(ct.parent, par);
+            link_wrench_up(rec, par, F, M, par + 12, par + 15);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) par[18 + i] += A[i];
+            rput(ct.parent, par);
+        }
+    }
+}
+
+// The same on the serial chain of link_chain_torques, everything in registers.
+//   wrench(k, f[3], m[3])   the wrench on op k's link        jout(dof, dS/dq, tau)
+template <int LINKS, int NJ, class ROW, class WRENCH, class JOUT>
+DRM_HD void link_chain_power_dq(ROW row, const float (&cs)[NJ], const float (&sn)[NJ], const float (&qd)[NJ], WRENCH wrench, JOUT jout) {
+    float p[LINKS][3], v[LINKS][3], w[LINKS][3], z[NJ][3];
+    {
+        LinkState cur;
+        link_state_root(cur);
+#pragma unroll
+        for (int k = 0; k < LINKS; ++k) {
+            const OpFT o = load_ft(row(k));
+            float J[9], t[3];
+            link_joint_transform(o, k < NJ, false, 0.0f, k < NJ ? cs[k] : 1.0f, k < NJ ? sn[k] : 0.0f, J, t);
+            link_step<true, false>(J, t, k < NJ, false, k < NJ ? qd[k] : 0.0f, 0.0f, cur);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                p[k][i] = cur.p[i]; v[k][i] = cur.v[i]; w[k][i] = cur.w[i];
+                if (k < NJ) z[k < NJ ? k : 0][i] = cur.R[3 * i + 2];
+            }
+        }
+    }
+    float Fc[3] = {0.0f, 0.0f, 0.0f}, Mc[3] = {0.0f, 0.0f, 0.0f}, A[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = LINKS - 1; k >= 0; --k) {
+        float F[3], M[3];
+        wrench(k, F, M);
+        link_power_own(v[k], w[k], F, M, A);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { F[i] += Fc[i]; M[i] += Mc[i]; }
+        if (k < NJ) jout(k, link_joint_power_dq(z[k < NJ ? k : 0], v[k], w[k], F, M, A, false), link_joint_torque(z[k < NJ ? k : 0], F, M, false));
         if (k > 0) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) { Fc[i] = 0.0f; Mc[i] = 0.0f; }

@@ -2004,21 +2004,25 @@ class DifferentiableRobotModel(torch.nn.Module):
         return LinkMotion(*[x[0] if (unbatched and x is not None) else x for x in outs])
 
     def compute_link_velocities(self, q: torch.Tensor, qd: torch.Tensor, link_names: Optional[List[str]] = None, *,
-                                _composed: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                                differentiable_q: bool = False, _composed: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """(linear_velocity, angular_velocity) [B, L, 3] of compute_link_motion(q, qd, link_names=link_names), to the bit, from the same
         launch with the two velocity arrays alone requested — and DIFFERENTIABLE once with respect to qd: the backward is the
         compute_external_torques launch with (forces, torques) := (grad_linear, grad_angular) (autograd._LinkAdjoint; a second backward
-        raises).  There is NO gradient with respect to q — it needs the kinematic Hessian, which is out of scope: with grad mode on a q
-        that requires grad raises ValueError; pass q.detach()."""
+        raises).  By default there is NO gradient with respect to q: with grad mode on a q that requires grad raises ValueError; pass
+        q.detach().  ``differentiable_q=True`` opts in: q may require grad, the forward values are the same bits, and the backward is ONE
+        drm_link_power_dq launch — grad_q = d/dq [sum_l g_lin_l . v_l + g_ang_l . w_l] at fixed qd, and grad_qd from the same launch
+        when qd needs one too (compute_link_power_gradient is that launch without autograd).  Still first order only."""
         unbatched, q, (qd,) = self._links_args(q, [(qd, "qd")], (self._n_dofs,))
         assert qd is not None, "qd must be given"
-        self._refuse_grad_q(q, "compute_link_velocities")
+        if not differentiable_q:
+            self._refuse_grad_q(q, "compute_link_velocities")
         self._require_device()
         with torch.no_grad():
             dw, T, sel, identity = self._links_plan(link_names)
             ops_f = self._ops_f(dw).detach()
-        if torch.is_grad_enabled() and qd.requires_grad:
-            lin, ang = _LinkAdjoint.apply(False, q.detach(), qd, None, dw.program, ops_f, dw.ops_i, T, self._n_dofs, bool(_composed))
+        if torch.is_grad_enabled() and (qd.requires_grad or (differentiable_q and q.requires_grad)):
+            lin, ang = _LinkAdjoint.apply(False, q if differentiable_q else q.detach(), qd, None, dw.program, ops_f, dw.ops_i, T,
+                                          self._n_dofs, bool(_composed), bool(differentiable_q))
         else:
             with torch.no_grad():
                 out = backend.link_motion(dw.program, ops_f, dw.ops_i, q.detach(), qd.detach(), None, T, self._n_dofs,
@@ -2028,7 +2032,8 @@ class DifferentiableRobotModel(torch.nn.Module):
         return (lin[0], ang[0]) if unbatched else (lin, ang)
 
     def compute_external_torques(self, q: torch.Tensor, forces: Optional[torch.Tensor], torques: Optional[torch.Tensor] = None,
-                                 link_names: Optional[List[str]] = None, *, _composed: bool = False) -> torch.Tensor:
+                                 link_names: Optional[List[str]] = None, *, differentiable_q: bool = False,
+                                 _composed: bool = False) -> torch.Tensor:
         """tau_ext [B, n] = sum_l lin_jac_l^T forces[:, l] + ang_jac_l^T torques[:, l]: the joint torques of external wrenches on the
         named links (None: every link in get_link_names() order) — contact forces, a payload, a wrist force/torque reading — with
         lin_jac_l, ang_jac_l compute_endeffector_jacobian's outputs for link l.  ``forces`` / ``torques`` [B, L, 3] are in WORLD axes
@@ -2040,9 +2045,11 @@ class DifferentiableRobotModel(torch.nn.Module):
         ONE kernel launch (csrc/drm_links.hip drm_external_torques): a sweep outwards for the poses and one inwards for the wrenches,
         instead of one Jacobian launch and two einsums per loaded link.  It is the adjoint of compute_link_velocities:
         sum_l f_l . v_l + m_l . w_l == tau_ext . qd for every qd.  DIFFERENTIABLE once with respect to forces and torques: the backward
-        is the link-motion launch with qd := grad_tau (autograd._LinkAdjoint; a second backward raises).  There is NO gradient with
-        respect to q — it needs the kinematic Hessian, which is out of scope: with grad mode on a q that requires grad raises
-        ValueError; pass q.detach().  A row whose q is not finite (or beyond 1e5) returns NaN and changes no other row; a wrench
+        is the link-motion launch with qd := grad_tau (autograd._LinkAdjoint; a second backward raises).  By default there is NO
+        gradient with respect to q: with grad mode on a q that requires grad raises ValueError; pass q.detach().
+        ``differentiable_q=True`` opts in: q may require grad, the forward values are the same bits, and grad_q = d/dq [tau_ext .
+        g_tau] comes from ONE drm_link_power_dq launch with qd := grad_tau (compute_link_power_gradient is that launch without
+        autograd).  Still first order only.  A row whose q is not finite (or beyond 1e5) returns NaN and changes no other row; a wrench
         component that is not finite makes the torques of that link's ancestor joints non-finite and changes nothing else.  Devices,
         joint models, learnable links and ``_composed``: as for compute_link_motion."""
         if forces is None and torques is None:
@@ -2050,20 +2057,49 @@ class DifferentiableRobotModel(torch.nn.Module):
         with torch.no_grad():
             dw, T, sel, identity = self._links_plan(link_names)
         unbatched, q, (forces, torques) = self._links_args(q, [(forces, "forces"), (torques, "torques")], (int(sel.numel()), 3))
-        self._refuse_grad_q(q, "compute_external_torques")
+        if not differentiable_q:
+            self._refuse_grad_q(q, "compute_external_torques")
         self._require_device()
         with torch.no_grad():
             ops_f = self._ops_f(dw).detach()
-        needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (forces, torques))
-        with torch.set_grad_enabled(needs_grad):
+        wrench_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (forces, torques))
+        needs_grad = wrench_grad or (torch.is_grad_enabled() and bool(differentiable_q) and q.requires_grad)
+        with torch.set_grad_enabled(wrench_grad):
             f, m = self._links_scatter(forces, sel, T, identity), self._links_scatter(torques, sel, T, identity)
         if needs_grad:
-            tau = _LinkAdjoint.apply(True, q.detach(), f, m, dw.program, ops_f, dw.ops_i, T, self._n_dofs, bool(_composed))
+            tau = _LinkAdjoint.apply(True, q if differentiable_q else q.detach(), f, m, dw.program, ops_f, dw.ops_i, T, self._n_dofs,
+                                     bool(_composed), bool(differentiable_q))
         else:
             with torch.no_grad():
                 tau = backend.external_torques(dw.program, ops_f, dw.ops_i, q.detach(), f.detach() if f is not None else None,
                                                m.detach() if m is not None else None, T, self._n_dofs, composed=bool(_composed))
         return tau[0] if unbatched else tau
+
+    def compute_link_power_gradient(self, q: torch.Tensor, qd: torch.Tensor, forces: Optional[torch.Tensor],
+                                    torques: Optional[torch.Tensor] = None, link_names: Optional[List[str]] = None, *,
+                                    _composed: bool = False) -> torch.Tensor:
+        """dpower_dq [B, n] = dS/dq of the power of external wrenches on the named links,
+            S(q; qd, forces, torques) = sum_l forces_l . v_l + torques_l . w_l = compute_external_torques(q, forces, torques) . qd,
+        with qd and the wrenches held fixed and (v_l, w_l) = compute_link_velocities(q, qd).  It is the vector-Jacobian product in q
+        of BOTH methods: of the velocities under the cotangents (forces, torques), of the torques under the cotangent qd — what their
+        ``differentiable_q=True`` backward launches, here for callers who want it without autograd.  ONE kernel launch
+        (csrc/drm_links.hip drm_link_power_dq): the two sweeps of compute_external_torques with the velocities carried outwards and one
+        more 3-vector inwards; no kinematic Hessian, no per-link Jacobian.  Argument handling, ``link_names``, non-finite rows and
+        wrenches, devices and ``_composed``: compute_external_torques'.  No autograd history."""
+        if forces is None and torques is None:
+            raise ValueError("forces and torques are both None")
+        with torch.no_grad():
+            dw, T, sel, identity = self._links_plan(link_names)
+        unbatched, q, (forces, torques) = self._links_args(q, [(forces, "forces"), (torques, "torques")], (int(sel.numel()), 3))
+        assert isinstance(qd, torch.Tensor) and tuple(qd.shape) == ((self._n_dofs,) if unbatched else tuple(q.shape)), "qd must be like q"
+        qd = qd.unsqueeze(0) if unbatched else qd
+        self._require_device()
+        with torch.no_grad():
+            f, m = self._links_scatter(forces, sel, T, identity), self._links_scatter(torques, sel, T, identity)
+            dq, _ = backend.link_power_dq(dw.program, self._ops_f(dw).detach(), dw.ops_i, q.detach(), qd.detach(),
+                                          f.detach() if f is not None else None, m.detach() if m is not None else None, T, self._n_dofs,
+                                          composed=bool(_composed))
+        return dq[0] if unbatched else dq
 
     # ------------------------------------------------------------------ plane contact and joint-limit springs
     def _contact_plan(self, contact, link_names, joint_limits):

@@ -711,6 +711,34 @@ int drm_external_torques(const drm_walk *walk, const float *q, const float *forc
                          int32_t flags, float *tau, float *scratch, void *stream);
 
 /*
+ * The q-gradient of both link sweeps in one call (additive to ABI 15).  The two are the two sides of one scalar, the power of the
+ * wrenches,
+ *   S(q; qd, force, torque) = sum_t force_t . lin_vel_t + torque_t . ang_vel_t = tau(q; force, torque) . qd,
+ * so dS/dq with qd, force and torque held fixed is the q-gradient of drm_link_motion's velocities under the cotangents
+ * (force, torque) := (g_lin_vel, g_ang_vel), and the q-gradient of drm_external_torques under the cotangent qd := g_tau.  No
+ * kinematic Hessian is formed: the two sweeps of drm_external_torques with the velocities carried outwards and one more 3-vector
+ * carried inwards (csrc/drm_links.hpp link_power_dq_walk).
+ *   dq   [B, n]  dS/dq.  Columns of DoFs that no target's chain crosses are written as zeros.
+ *   tau  [B, n]  optional (NULL: not stored): drm_external_torques' output on the same q, force and torque, to the bit — the backward
+ *                of the velocities gets grad_q and grad_qd from one launch.
+ * walk, q, force, torque, n_targets, flags (DRM_LINKS_COMPOSED), scratch and stream: drm_external_torques'; qd [B, n] must be given.
+ * The same two kernels: fused for the arm chain of 8 targets on full 64-row tiles with every pointer 16-byte aligned (q, qd, the two
+ * wrench tiles in and dq, tau out through LDS in 16-byte accesses: 248 B in, 28 or 56 B out per row), one lane per row over the ops
+ * elsewhere.  A row with a q or qd that is not finite, or with a |q| beyond 1e5, gets NaN in dq and tau and changes no bit of any
+ * other row.  A wrench component that is not finite makes the dq and tau entries of that link's ancestor joints non-finite and
+ * changes nothing else.
+ *   scratch   drm_link_power_dq_scratch_floats' floats (the _aligned form returns the same): the rows' state where 64 rows of it do
+ *             not fit the general kernel's LDS budget — 21 n_ops + 24 n_slots floats per row, at most 2 048 tiles of 64 rows at a
+ *             time; 0 (scratch may be NULL) for chains of up to 6 ops
+ * DRM_ERR_INVALID for a NULL q, qd or dq, no wrench input, a negative B or an n_targets outside [1, n_ops]; B == 0 returns DRM_OK.
+ * Asynchronous on `stream`, never a host synchronisation, no allocation.
+ */
+int64_t drm_link_power_dq_scratch_floats(const drm_walk *walk, int64_t B);
+int64_t drm_link_power_dq_scratch_floats_aligned(const drm_walk *walk, int64_t B);
+int drm_link_power_dq(const drm_walk *walk, const float *q, const float *qd, const float *force, const float *torque, int64_t B,
+                      int32_t n_targets, int32_t flags, float *dq, float *tau, float *scratch, void *stream);
+
+/*
  * Contact: spheres on the links against ONE plane (a penalty spring-damper with regularised Coulomb friction) and spring-dampers at the
  * joint limits, as joint torques of one state (drm_contact_torques) and inside a rollout (drm_contact_rollout), where they depend on
  * the state of every step and so cannot be handed to drm_forward_dynamics_rollout in advance.  The law (csrc/drm_contact.hpp), with
