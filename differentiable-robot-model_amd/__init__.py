@@ -23,6 +23,11 @@ from .robot_model import (  # noqa: F401
     JointLimitSprings,
     ContactTorques,
     ContactRollout,
+    CollisionSpheres,
+    CollisionWorld,
+    CollisionGeometry,
+    CollisionCost,
+    SphereDistances,
 )
 
 __version__ = "0.1.0"

@@ -727,6 +727,26 @@ class _Energy(torch.autograd.Function):
         return grad_q, grad_qd, None, None, None, None
 
 
+class _CollisionCost(torch.autograd.Function):
+    """(cost [B], dcost_dq [B, n]) of backend.collision_cost (csrc/drm_collision.hip).  The forward launch hands out the gradient with
+    the cost, so the backward launches nothing: grad_q = g[:, None] * dcost_dq.  dcost_dq itself is not differentiable.  First order
+    only (once_differentiable): a second backward through it raises.  The walk's table and the geometry are constants of the node."""
+
+    @staticmethod
+    def forward(ctx, q, prog, ops_f, ops_i, n_targets, n_dofs, tables, params, composed):
+        cost, dq = backend.collision_cost(prog, ops_f, ops_i, q.detach(), n_targets, n_dofs, tables, params, composed=composed)
+        ctx.save_for_backward(dq)
+        ctx.q_dtype = q.dtype
+        ctx.mark_non_differentiable(dq)
+        return cost, dq
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        (dq,) = ctx.saved_tensors
+        return ((g[:, None] * dq).to(ctx.q_dtype),) + (None,) * 8
+
+
 class _LinkAdjoint(torch.autograd.Function):
     """The two adjoint sweeps over a many-target FK walk (backend.link_motion, backend.external_torques, csrc/drm_links.hip) as ONE
     node, in either direction.  With J the stacked link Jacobians [lin_jac_t; ang_jac_t] at q:

@@ -66,6 +66,27 @@ class DrmContactPlane(ctypes.Structure):
                 ("friction", ctypes.c_float), ("friction_slope", ctypes.c_float)]
 
 
+class DrmCollisionSpheres(ctypes.Structure):
+    """Mirror of ``struct drm_collision_spheres`` (include/drm_hip.h)."""
+    _fields_ = [("spheres", ctypes.c_void_p), ("start", ctypes.c_void_p), ("n_spheres", ctypes.c_int32)]
+
+
+class DrmCollisionWorld(ctypes.Structure):
+    """Mirror of ``struct drm_collision_world`` (include/drm_hip.h)."""
+    _fields_ = [("spheres", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("n_spheres", ctypes.c_int32), ("n_boxes", ctypes.c_int32)]
+
+
+class DrmCollisionPairs(ctypes.Structure):
+    """Mirror of ``struct drm_collision_pairs`` (include/drm_hip.h)."""
+    _fields_ = [("pairs", ctypes.c_void_p), ("n_pairs", ctypes.c_int32)]
+
+
+class DrmCollisionParams(ctypes.Structure):
+    """Mirror of ``struct drm_collision_params`` (include/drm_hip.h)."""
+    _fields_ = [("world_weight", ctypes.c_float), ("world_activation", ctypes.c_float), ("self_weight", ctypes.c_float),
+                ("self_activation", ctypes.c_float)]
+
+
 class DrmJointSprings(ctypes.Structure):
     """Mirror of ``struct drm_joint_springs`` (include/drm_hip.h)."""
     _fields_ = [("stiffness", ctypes.c_float), ("damping", ctypes.c_float)]
@@ -116,7 +137,9 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
            "drm_link_power_dq", "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
            "drm_contact_torques", "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
-           "drm_contact_rollout", "drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned")
+           "drm_contact_rollout", "drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned",
+           "drm_collision_cost", "drm_collision_cost_scratch_floats", "drm_collision_cost_scratch_floats_aligned",
+           "drm_sphere_distances", "drm_sphere_distances_scratch_floats", "drm_sphere_distances_scratch_floats_aligned")
 
 
 def library_for(device):
@@ -231,6 +254,16 @@ def load_library(path: str = None, kind: str = "cuda"):
         lib.drm_contact_torques.argtypes = [wp, vp, vp, i64, i32, pp, vp, sp, vp, vp, i32, vp, vp, vp, vp, vp]
         lib.drm_contact_rollout.restype = ctypes.c_int
         lib.drm_contact_rollout.argtypes = [wp, wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, i32, pp, vp, sp, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("drm_collision_cost_scratch_floats", "drm_sphere_distances_scratch_floats"):
+            getattr(lib, name).restype = i64
+            getattr(lib, name).argtypes = [wp, i64, i32]
+            getattr(lib, name + "_aligned").restype = i64
+            getattr(lib, name + "_aligned").argtypes = [wp, i64, i32, i32, i32, i32]
+        csp, cwp, cpp = ctypes.POINTER(DrmCollisionSpheres), ctypes.POINTER(DrmCollisionWorld), ctypes.POINTER(DrmCollisionPairs)
+        lib.drm_collision_cost.restype = ctypes.c_int
+        lib.drm_collision_cost.argtypes = [wp, vp, i64, i32, csp, cwp, cpp, ctypes.POINTER(DrmCollisionParams), i32, vp, vp, vp, vp]
+        lib.drm_sphere_distances.restype = ctypes.c_int
+        lib.drm_sphere_distances.argtypes = [wp, vp, i64, i32, csp, cwp, cpp, i32, vp, vp, vp, vp, vp]
         lib.drm_operational_space.restype = ctypes.c_int
         lib.drm_operational_space.argtypes = [wp, wp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]
         for name in ("drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned"):
@@ -637,12 +670,12 @@ def _rnea_scratch(lib, walk, B, device):
     return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
 
 
-def _scratch(lib, base: str, walks, B: int, composed: bool, device):
+def _scratch(lib, base: str, walks, B: int, composed: bool, device, extra=()):
     """The scratch of entry point ``base`` over B rows of ``walks`` (None: not needed).  The callers' tensors come from _dev_f32 /
     _outputs / torch.empty, 16-byte aligned, so the ``_aligned`` query sizes the call; ``composed`` (the entry point's DRM_*_COMPOSED
-    flag) takes the composed path / general kernel on every row: the size for any pointers."""
+    flag) takes the composed path / general kernel on every row: the size for any pointers.  ``extra``: what the query takes after B."""
     query = getattr(lib, base + ("_scratch_floats" if composed else "_scratch_floats_aligned"))
-    need = int(query(*[ctypes.byref(w) for w in walks], B))
+    need = int(query(*[ctypes.byref(w) for w in walks], B, *extra))
     return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
 
 
@@ -1317,6 +1350,96 @@ def contact_torques(prog: WalkProgram, ops_f, ops_i, q, qd, n_targets: int, n_do
                                        LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(force), ptr(moment), ptr(scratch),
                                        _stream(q.device)), lib)
     return tau, force, moment
+
+
+def _collision_structs(tables, device):
+    """(drm_collision_spheres, drm_collision_world or None, drm_collision_pairs or None, S) of ``tables`` = (spheres [S, 4] float32,
+    start [T + 2] int32, world spheres [Ms, 4] or None, boxes [Mb, 16] or None, pairs [P, 2] int32 or None), all contiguous on
+    ``device``; the world is None when both of its tables are.  The C side validates the values."""
+    spheres, start, ws, wb, pairs = tables
+    for name, t, dt in (("spheres", spheres, torch.float32), ("start", start, torch.int32), ("world spheres", ws, torch.float32),
+                        ("boxes", wb, torch.float32), ("pairs", pairs, torch.int32)):
+        if t is not None and (t.device != device or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, device))
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    S = int(spheres.shape[0])
+    sp = DrmCollisionSpheres(ptr(spheres), ptr(start), S)
+    world = None
+    if ws is not None or wb is not None:
+        world = DrmCollisionWorld(ptr(ws), ptr(wb), int(ws.shape[0]) if ws is not None else 0, int(wb.shape[0]) if wb is not None else 0)
+    pr = DrmCollisionPairs(ptr(pairs), int(pairs.shape[0])) if pairs is not None else None
+    return sp, world, pr, S
+
+
+def _collision_scratch(lib, base: str, walk, B: int, n_targets: int, tables, composed: bool, device):
+    """_scratch of a collision entry point: the ``_aligned`` query is told the targets and the sizes of the tables, so a call
+    that the fused kernel takes allocates for its B % 64 tail rows alone (nothing when there are none)."""
+    if composed:
+        return _scratch(lib, base, (walk,), B, True, device, extra=(int(tables[0].shape[0]),))
+    count = lambda t: int(t.shape[0]) if t is not None else 0
+    return _scratch(lib, base, (walk,), B, False, device,
+                    extra=(n_targets, count(tables[0]), count(tables[2]) + count(tables[3]), count(tables[4])))
+
+
+def collision_cost(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs: int, tables, params, want=("cost", "dq"),
+                   composed: bool = False):
+    """(cost [B], dq [B, n]): the collision cost of spheres on the T targets of a many-target FK walk against a world of spheres and
+    boxes and against each other, and its q-gradient, in one launch (include/drm_hip.h drm_collision_cost).  ``tables``:
+    _collision_structs; ``params`` = (world_weight, world_activation, self_weight, self_activation); ``want`` names the outputs to
+    compute, the other comes back as None (without "dq" no sweep inwards runs).  ``composed``: as for link_motion."""
+    lib = _lib_of(q, "q", ops_f)
+    q = _dev_f32(q, "q", n_dofs)
+    B = int(q.shape[0])
+    want = tuple(want)
+    if not want or any(w not in ("cost", "dq") for w in want):
+        raise ValueError("want must name at least one of ('cost', 'dq')")
+    sp, world, pr, S = _collision_structs(tables, q.device)
+    made = dict(zip(want, _outputs(q.device, *[{"cost": (B,), "dq": (B, n_dofs)}[w] for w in want])))
+    cost, dq = made.get("cost"), made.get("dq")
+    if B == 0:
+        return cost, dq
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _collision_scratch(lib, "drm_collision_cost", walk, B, n_targets, tables, composed, q.device)
+    par = DrmCollisionParams(*[float(x) for x in params])
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ref = lambda st: ctypes.byref(st) if st is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_collision_cost(ctypes.byref(walk), q.data_ptr(), B, n_targets, ctypes.byref(sp), ref(world), ref(pr), ctypes.byref(par),
+                                      LINKS_COMPOSED if composed else 0, ptr(cost), ptr(dq), ptr(scratch), _stream(q.device)), lib)
+    return cost, dq
+
+
+SPHERE_DISTANCE_OUTPUTS = ("center", "world_distance", "self_distance")
+
+
+def sphere_distances(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs: int, tables, want=SPHERE_DISTANCE_OUTPUTS,
+                     composed: bool = False):
+    """(center [B, S, 3], world_distance [B, S], self_distance [B, S]) of the spheres of collision_cost, in the grouped order of the
+    sphere table, in one launch (include/drm_hip.h drm_sphere_distances): the world centres, the least clearance to an obstacle and
+    the least clearance over the pairs a sphere is in (+inf without a world / without a pair).  ``want`` names the outputs to compute;
+    the others come back as None."""
+    lib = _lib_of(q, "q", ops_f)
+    q = _dev_f32(q, "q", n_dofs)
+    B = int(q.shape[0])
+    want = tuple(want)
+    if not want or any(w not in SPHERE_DISTANCE_OUTPUTS for w in want):
+        raise ValueError("want must name at least one of %s" % (SPHERE_DISTANCE_OUTPUTS,))
+    sp, world, pr, S = _collision_structs(tables, q.device)
+    shapes = {"center": (B, S, 3), "world_distance": (B, S), "self_distance": (B, S)}
+    made = dict(zip(want, _outputs(q.device, *[shapes[w] for w in want])))
+    outs = tuple(made.get(name) for name in SPHERE_DISTANCE_OUTPUTS)
+    if B == 0:
+        return outs
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _collision_scratch(lib, "drm_sphere_distances", walk, B, n_targets, tables, composed, q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ref = lambda st: ctypes.byref(st) if st is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_sphere_distances(ctypes.byref(walk), q.data_ptr(), B, n_targets, ctypes.byref(sp), ref(world), ref(pr),
+                                        LINKS_COMPOSED if composed else 0, *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
+    return outs
 
 
 def contact_rollout(dyn, links, q0, qd0, tau, dt: float, gravity: bool, damping: bool, explicit: bool, n_targets: int, n_dofs: int,

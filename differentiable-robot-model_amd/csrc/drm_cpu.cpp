@@ -32,6 +32,7 @@
 #include "drm_energy.hpp"
 #include "drm_links.hpp"
 #include "drm_contact.hpp"
+#include "drm_collision.hpp"
 #include "drm_rollout.hpp"
 #include "drm_rows.hpp"
 
@@ -553,6 +554,78 @@ void contact_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q,
         }
     }
 }
+// what drm_collision_cost and drm_sphere_distances ask of their arguments (drm_collision.hip coll_check)
+int collision_check(const drm_walk *w, const float *q, int64_t B, int T, const drm_collision_spheres *spheres, const drm_collision_world *world,
+                    const drm_collision_pairs *pairs, drm::CollTables &t) {
+    t = drm::CollTables{};
+    if (int rc = check_sweep_walk(w)) return rc;
+    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
+    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
+    if (!spheres || !spheres->spheres || !spheres->start) return fail(DRM_ERR_INVALID, "spheres, their table and their offsets must not be NULL");
+    if (spheres->n_spheres < 1) return fail(DRM_ERR_INVALID, "at least one sphere");
+    t.spheres = spheres->spheres; t.start = spheres->start; t.S = spheres->n_spheres; t.T = T;
+    if (world) {
+        if (world->n_spheres < 0 || world->n_boxes < 0) return fail(DRM_ERR_INVALID, "negative obstacle count");
+        if ((world->n_spheres > 0 && !world->spheres) || (world->n_boxes > 0 && !world->boxes))
+            return fail(DRM_ERR_INVALID, "a world table is NULL");
+        t.ws = world->spheres; t.n_ws = world->n_spheres; t.wb = world->boxes; t.n_wb = world->n_boxes;
+    }
+    if (pairs) {
+        if (pairs->n_pairs < 0) return fail(DRM_ERR_INVALID, "negative pair count");
+        if (pairs->n_pairs > 0 && !pairs->pairs) return fail(DRM_ERR_INVALID, "the pair list is NULL");
+        t.pairs = pairs->pairs; t.P = pairs->n_pairs;
+    }
+    t.world = t.self = drm::coll_law_make(0.0f, 1.0f);
+    return DRM_OK;
+}
+// drm_collision_cost (cost, dq) / drm_sphere_distances (center, wd, sd) of `rows` rows (all pointers at the first of them, any may be
+// NULL): the targets' frames by the chain form where drm_collision.hip would launch its fused kernel, by the general walk elsewhere;
+// the law per row (drm_collision.hpp coll_row); dq by link_torques_host_rows.
+void collision_host_rows(const drm_walk *w, const drm::CollTables &t, const float *q, int64_t rows, int flags, float *cost, float *dq,
+                         float *center, float *wd, float *sd) {
+    const int n = w->n_dofs, T = t.T, S = t.S;
+    const Ctl ctl(w);
+    HostRecords<drm::LINKS_SLOT_FLOATS> slots(w->n_slots);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const bool chain = links_chain_walk(w, T, flags) && drm::coll_within_caps(S, t.n_ws + t.n_wb, t.P);
+    std::vector<float> R((size_t)9 * T), p((size_t)3 * T), cen(center ? 0 : (size_t)3 * S);
+    std::vector<float> F(dq ? (size_t)rows * T * 3 : 0), M(F.size());
+    auto row = [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; };
+    for (int64_t b = 0; b < rows; ++b) {
+        const float *qr = q + b * n;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(qr[d], 0.0f);
+        auto emit = [&](int k, const drm::LinkState &st) {
+            if (k >= T) return;
+            for (int i = 0; i < 9; ++i) R[9 * k + i] = st.R[i];
+            for (int i = 0; i < 3; ++i) p[3 * k + i] = st.p[i];
+        };
+        if (chain) {
+            float qv[7], cs[7], sn[7];
+            const float zero[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            for (int d = 0; d < 7; ++d) qv[d] = bad ? 0.0f : qr[d];
+            drm::chain_trig<7>(qv, cs, sn);
+            drm::link_chain_motion<8, 7, false, false>(row, cs, sn, zero, zero, emit);
+        } else {
+            drm::link_motion_walk<false, false>(
+                w->n_ops, w->n_slots, ctl, row,
+                [&](int d, float &x, float &v, float &acc) { x = bad ? 0.0f : qr[d]; v = 0.0f; acc = 0.0f; },
+                [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, emit);
+        }
+        float *cr = center ? center + b * S * 3 : cen.data();
+        const float c = drm::coll_row(t, R.data(), p.data(), cr, dq ? &F[(size_t)b * T * 3] : nullptr, dq ? &M[(size_t)b * T * 3] : nullptr,
+                                      wd ? wd + b * S : nullptr, sd ? sd + b * S : nullptr);
+        if (cost) cost[b] = bad ? nan : c;
+        if (bad)
+            for (int s = 0; s < S; ++s) {
+                if (center) cr[3 * s] = cr[3 * s + 1] = cr[3 * s + 2] = nan;
+                if (wd) wd[b * S + s] = nan;
+                if (sd) sd[b * S + s] = nan;
+            }
+    }
+    if (dq) link_torques_host_rows(w, q, F.data(), M.data(), 0, rows, T, flags, dq);
+}
 } // namespace
 
 extern "C" {
@@ -906,6 +979,47 @@ int drm_contact_torques(const drm_walk *lw, const float *q, const float *qd, int
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         contact_host_rows(lw, a, q + b0 * n, qd + b0 * n, nullptr, rows, T, n, flags, true, tau + b0 * n,
                           force ? force + b0 * T * 3 : nullptr, moment ? moment + b0 * T * 3 : nullptr);
+    });
+    return DRM_OK;
+}
+
+// Collision cost and sphere distances (drm_collision.hpp): every chunk of rows runs collision_host_rows.
+int64_t drm_collision_cost_scratch_floats(const drm_walk *, int64_t, int32_t) { return 0; }
+int64_t drm_collision_cost_scratch_floats_aligned(const drm_walk *, int64_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
+int64_t drm_sphere_distances_scratch_floats(const drm_walk *, int64_t, int32_t) { return 0; }
+int64_t drm_sphere_distances_scratch_floats_aligned(const drm_walk *, int64_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+int drm_collision_cost(const drm_walk *w, const float *q, int64_t B, int32_t T, const drm_collision_spheres *spheres,
+                       const drm_collision_world *world, const drm_collision_pairs *pairs, const drm_collision_params *params, int32_t flags,
+                       float *cost, float *dq, float *, void *) {
+    drm::CollTables t;
+    if (int rc = collision_check(w, q, B, T, spheres, world, pairs, t)) return rc;
+    if (!world && !pairs) return fail(DRM_ERR_INVALID, "neither a world nor pairs");
+    if (!params) return fail(DRM_ERR_INVALID, "params must not be NULL");
+    if (!cost && !dq) return fail(DRM_ERR_INVALID, "cost and dq are both NULL");
+    if (world && !drm::coll_law_ok(params->world_weight, params->world_activation))
+        return fail(DRM_ERR_INVALID, "the world weight must be finite and >= 0, its activation distance finite and > 0");
+    if (pairs && !drm::coll_law_ok(params->self_weight, params->self_activation))
+        return fail(DRM_ERR_INVALID, "the self weight must be finite and >= 0, its activation distance finite and > 0");
+    if (world) t.world = drm::coll_law_make(params->world_weight, params->world_activation);
+    if (pairs) t.self = drm::coll_law_make(params->self_weight, params->self_activation);
+    const int n = w->n_dofs;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        collision_host_rows(w, t, q + b0 * n, rows, flags, cost ? cost + b0 : nullptr, dq ? dq + b0 * n : nullptr, nullptr, nullptr, nullptr);
+    });
+    return DRM_OK;
+}
+
+int drm_sphere_distances(const drm_walk *w, const float *q, int64_t B, int32_t T, const drm_collision_spheres *spheres,
+                         const drm_collision_world *world, const drm_collision_pairs *pairs, int32_t flags, float *center, float *wd,
+                         float *sd, float *, void *) {
+    drm::CollTables t;
+    if (int rc = collision_check(w, q, B, T, spheres, world, pairs, t)) return rc;
+    if (!center && !wd && !sd) return fail(DRM_ERR_INVALID, "every output is NULL");
+    const int n = w->n_dofs, S = t.S;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        collision_host_rows(w, t, q + b0 * n, rows, flags, nullptr, nullptr, center ? center + b0 * S * 3 : nullptr, wd ? wd + b0 * S : nullptr,
+                            sd ? sd + b0 * S : nullptr);
     });
     return DRM_OK;
 }

@@ -24,10 +24,10 @@ import numpy as np
 import torch
 
 from . import backend
-from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, RobotSpec, WalkProgram, build_robot_spec, build_walk, fold_link_table,
-                      foldable_links, identity_table_row, virtual_row_constants)
+from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, OPI_OUT, OPI_PERM, _PERM, RobotSpec, WalkProgram, build_robot_spec,
+                      build_walk, fold_link_table, foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
-                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _quat_grad_to_rot)
+                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _CollisionCost, _quat_grad_to_rot)
 from .rigid_body import DifferentiableRigidBody, LinkPose, LinkVelocity
 from .urdf_utils import URDFRobotModel
 
@@ -222,6 +222,106 @@ class ContactRollout(NamedTuple):
     q: torch.Tensor                     # [T, B, n] the positions after steps 1 .. T
     qd: torch.Tensor                    # [T, B, n] the velocities after steps 1 .. T
     qdd: Optional[torch.Tensor]         # [T, B, n] the acceleration OF step t (at the state before it); None unless asked for
+
+
+def _float_array(x, shape, name):
+    """``x`` as a float32 numpy array of ``shape`` (-1: any length), finite"""
+    a = np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32)
+    if a.ndim != len(shape) or any(want >= 0 and got != want for got, want in zip(a.shape, shape)):
+        raise ValueError("%s must have shape %s (got %s)" % (name, list(shape), list(a.shape)))
+    if not np.isfinite(a).all():
+        raise ValueError("%s must be finite" % name)
+    return a
+
+
+class CollisionSpheres:
+    """The robot as spheres fixed to its links: sphere s sits on link ``link_names[s]`` with centre ``centers[s]`` in that link's own
+    URDF frame (the frame whose pose compute_forward_kinematics returns) and radius ``radii[s]`` >= 0.  Any order, any number per link;
+    spheres on the root are allowed (they never move: a constant of the cost, but they take part in self pairs)."""
+
+    def __init__(self, link_names, centers, radii):
+        self.link_names = [str(n) for n in link_names]
+        self.centers = _float_array(centers, (len(self.link_names), 3), "centers")
+        self.radii = _float_array(radii, (len(self.link_names),), "radii")
+        if not self.link_names:
+            raise ValueError("at least one sphere")
+        if (self.radii < 0).any():
+            raise ValueError("radii must be >= 0")
+
+
+class CollisionWorld:
+    """The obstacles, shared by every row of a batch: ``spheres`` [Ms, 4] = centre and radius; boxes with centres ``box_centers``
+    [Mb, 3], half extents ``box_half_extents`` [Mb, 3] >= 0 and rotations ``box_rotations`` [Mb, 3, 3] from box to world axes
+    (None: axis-aligned).  Either kind may be absent."""
+
+    def __init__(self, spheres=None, box_centers=None, box_half_extents=None, box_rotations=None):
+        self.spheres = _float_array(spheres, (-1, 4), "spheres") if spheres is not None else np.zeros((0, 4), np.float32)
+        if (self.spheres[:, 3] < 0).any():
+            raise ValueError("sphere radii must be >= 0")
+        if (box_centers is None) != (box_half_extents is None):
+            raise ValueError("boxes need box_centers and box_half_extents")
+        if box_centers is None:
+            if box_rotations is not None:
+                raise ValueError("box_rotations without boxes")
+            self.boxes = np.zeros((0, 16), np.float32)
+        else:
+            c = _float_array(box_centers, (-1, 3), "box_centers")
+            h = _float_array(box_half_extents, (len(c), 3), "box_half_extents")
+            if (h < 0).any():
+                raise ValueError("box_half_extents must be >= 0")
+            R = np.tile(np.eye(3, dtype=np.float32), (len(c), 1, 1)) if box_rotations is None else \
+                _float_array(box_rotations, (len(c), 3, 3), "box_rotations")
+            self.boxes = np.concatenate([c, h, R.reshape(len(c), 9), np.zeros((len(c), 1), np.float32)], axis=1).astype(np.float32)
+
+    @property
+    def n_obstacles(self):
+        return len(self.spheres) + len(self.boxes)
+
+
+class CollisionGeometry:
+    """What DifferentiableRobotModel.make_collision_geometry returns: the device tables of one sphere set, its self pairs and one
+    world (csrc/drm_collision.hpp), built once.  ``with_world`` swaps the obstacles and shares everything else."""
+
+    def __init__(self, model, walk_names, spheres, start, order, pairs, world_spheres, world_boxes):
+        self._model = model
+        self._walk_names = walk_names          # what _links_plan takes: the links of the walk
+        self.spheres, self.start = spheres, start      # [S, 4] float32 grouped by link, [T + 2] int32
+        self.order = order                     # [S] int64: grouped position of the caller's sphere s; None: the caller's order is grouped
+        self.pairs = pairs                     # [P, 2] int32 in grouped indices, or None
+        self.world_spheres, self.world_boxes = world_spheres, world_boxes      # [Ms, 4], [Mb, 16] or None
+
+    @property
+    def n_spheres(self):
+        return int(self.spheres.shape[0])
+
+    @property
+    def n_pairs(self):
+        return 0 if self.pairs is None else int(self.pairs.shape[0])
+
+    @property
+    def has_world(self):
+        return self.world_spheres is not None or self.world_boxes is not None
+
+    def tables(self):
+        return (self.spheres, self.start, self.world_spheres, self.world_boxes, self.pairs)
+
+    def with_world(self, world):
+        """The same spheres and pairs against another CollisionWorld (None: no obstacles)."""
+        ws, wb = self._model._collision_world_tables(world)
+        return CollisionGeometry(self._model, self._walk_names, self.spheres, self.start, self.order, self.pairs, ws, wb)
+
+
+class CollisionCost(NamedTuple):
+    """What DifferentiableRobotModel.compute_collision_cost returns."""
+    cost: torch.Tensor                  # [B] differentiable once with respect to q
+    dcost_dq: torch.Tensor              # [B, n] its gradient, from the same launch (no autograd history)
+
+
+class SphereDistances(NamedTuple):
+    """What DifferentiableRobotModel.compute_sphere_distances returns (no autograd history), in the caller's sphere order."""
+    center: torch.Tensor                # [B, S, 3] world centres
+    world_distance: torch.Tensor        # [B, S] least clearance to an obstacle (+inf without a world); < 0: penetration
+    self_distance: torch.Tensor         # [B, S] least clearance over the pairs the sphere is in (+inf without one)
 
 
 class DifferentiableRobotModel(torch.nn.Module):
@@ -2100,6 +2200,153 @@ class DifferentiableRobotModel(torch.nn.Module):
                                           f.detach() if f is not None else None, m.detach() if m is not None else None, T, self._n_dofs,
                                           composed=bool(_composed))
         return dq[0] if unbatched else dq
+
+    # ------------------------------------------------------------------ collision of spheres with a world and with each other
+    def _collision_world_tables(self, world):
+        """(spheres [Ms, 4] or None, boxes [Mb, 16] or None) on the device; both None without obstacles"""
+        if world is None:
+            return None, None
+        if not isinstance(world, CollisionWorld):
+            raise TypeError("world must be a CollisionWorld (or None)")
+        if world.n_obstacles == 0:
+            return None, None
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self._device)
+        return dev(world.spheres), dev(world.boxes)
+
+    def _collision_rep(self, link):
+        """the link a fixed-joint chain hangs on: a chain of fixed joints counts as one link"""
+        i = int(link)
+        while i > 0 and self._spec.dof[i] < 0:
+            i = int(self._spec.parent[i])
+        return i
+
+    def make_collision_geometry(self, spheres: CollisionSpheres, world: Optional[CollisionWorld] = None, self_pairs="auto", *,
+                                _subset_walk: bool = False) -> CollisionGeometry:
+        """The device tables of compute_collision_cost / compute_sphere_distances, built once: the spheres sorted by link (a stable
+        sort; results come back in the caller's order), their centres converted into the frames the kernels walk, the obstacles, and
+        the self-collision pairs.  ``self_pairs``: "auto" — every pair of spheres whose links are neither the same nor parent and
+        child, a chain of fixed joints counting as one link; None; or an explicit [P, 2] list in the caller's sphere indices
+        (i != j).  The walk is the one of compute_link_motion over every link, so links without a sphere cost nothing but an empty
+        group (``_subset_walk``: the walk over the links that carry spheres alone; for tests)."""
+        if not isinstance(spheres, CollisionSpheres):
+            raise TypeError("spheres must be a CollisionSpheres")
+        for name in spheres.link_names:
+            if name not in self._name_to_idx_map:
+                raise KeyError("unknown link %r" % name)
+        link_idx = [self._name_to_idx_map[name] for name in spheres.link_names]
+        walk_names = None
+        if _subset_walk:
+            walk_names = tuple(dict.fromkeys(spheres.link_names))
+        with torch.no_grad():
+            dw, T, sel, _ = self._links_plan(None if walk_names is None else list(walk_names))
+        names = self.get_link_names() if walk_names is None else list(walk_names)
+        slot = {self._name_to_idx_map[name]: int(t) for name, t in zip(names, sel.tolist())}      # T for the root
+        group = np.asarray([0 if slot[i] == T else slot[i] + 1 for i in link_idx], np.int64)
+        # the stored frame of target t is R~ = R P with (M P)[:, c] = d[c] M[:, pi[c]]: c~ = P^T c, c~[c] = d[c] c[pi[c]], exactly
+        ops = np.asarray(dw.program.ops_i)
+        code = {}
+        for k in range(dw.program.n_ops):
+            if ops[k, OPI_OUT] >= 0:
+                code[int(ops[k, OPI_OUT])] = int(ops[k, OPI_PERM])        # (a link of two ops: the frame of its last op)
+        centers = spheres.centers.copy()
+        for s_i, g in enumerate(group):
+            c = code[int(g) - 1] if g else 2
+            pi, sign = _PERM[c % 3], (-1.0 if c >= 3 else 1.0)
+            d = (1.0, sign, sign)
+            centers[s_i] = [d[k] * spheres.centers[s_i, pi[k]] for k in range(3)]
+        order = np.argsort(group, kind="stable")             # grouped position g holds the caller's sphere order[g]
+        inverse = np.empty_like(order)
+        inverse[order] = np.arange(len(order))
+        table = np.concatenate([centers, spheres.radii[:, None]], axis=1)[order].astype(np.float32)
+        start = np.searchsorted(group[order], np.arange(T + 2), side="left").astype(np.int32)
+        if isinstance(self_pairs, str):
+            if self_pairs != "auto":
+                raise ValueError("self_pairs must be 'auto', None or a [P, 2] list of sphere indices")
+            rep = [self._collision_rep(i) for i in link_idx]
+            up = [self._collision_rep(self._spec.parent[r]) if r > 0 else -1 for r in rep]
+            pairs = [(i, j) for i in range(len(rep)) for j in range(i + 1, len(rep))
+                     if rep[i] != rep[j] and up[i] != rep[j] and up[j] != rep[i]]
+            # (in grouped order, first sphere by first sphere: the kernels keep a run's gradient in registers)
+            pairs = sorted((min(inverse[i], inverse[j]), max(inverse[i], inverse[j])) for i, j in pairs)
+            pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        elif self_pairs is not None:
+            pairs = np.asarray(self_pairs.detach().cpu() if isinstance(self_pairs, torch.Tensor) else self_pairs, dtype=np.int64)
+            if pairs.ndim != 2 or pairs.shape[1] != 2:
+                raise ValueError("self_pairs must be [P, 2] (got %s)" % (list(pairs.shape),))
+            if pairs.size and (pairs.min() < 0 or pairs.max() >= len(group) or (pairs[:, 0] == pairs[:, 1]).any()):
+                raise ValueError("self_pairs must index the spheres, i != j")
+            pairs = inverse[pairs].astype(np.int32)
+        else:
+            pairs = None
+        if pairs is not None and len(pairs) == 0:
+            pairs = None
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self._device)
+        ws, wb = self._collision_world_tables(world)
+        identity = bool((order == np.arange(len(order))).all())
+        return CollisionGeometry(self, walk_names, dev(table), dev(start), None if identity else dev(inverse), None if pairs is None else dev(pairs),
+                                 ws, wb)
+
+    def _collision_args(self, q, geometry):
+        if not isinstance(geometry, CollisionGeometry) or geometry._model is not self:
+            raise TypeError("geometry must come from this model's make_collision_geometry")
+        if not isinstance(q, torch.Tensor):
+            raise TypeError("q must be a tensor")
+        assert q.device.type == self._device.type, "Input argument of different device as module: q"
+        assert q.ndim in [1, 2], "Input tensors must have ndim of 1 or 2."
+        assert q.shape[-1] == self._n_dofs
+        self._require_device()
+        with torch.no_grad():
+            dw, T, _, _ = self._links_plan(None if geometry._walk_names is None else list(geometry._walk_names))
+            ops_f = self._ops_f(dw).detach()
+        return q.ndim == 1, (q.unsqueeze(0) if q.ndim == 1 else q), dw, T, ops_f
+
+    def compute_collision_cost(self, q: torch.Tensor, geometry: CollisionGeometry, *, world_activation: float = 0.05,
+                               self_activation: float = 0.02, world_weight: float = 1.0, self_weight: float = 1.0,
+                               _composed: bool = False) -> CollisionCost:
+        """The collision cost of the geometry's spheres at q [B, n] and its gradient, from ONE launch (csrc/drm_collision.hip):
+            cost      [B]     world_weight sum_{s, m} phi(world_activation - d_sm) + self_weight sum_pairs phi(self_activation - d_ij)
+            dcost_dq  [B, n]  its gradient with respect to q
+        with d_sm the clearance of sphere s to obstacle m (signed distance of its centre minus its radius), d_ij = |x_i - x_j| - r_i -
+        r_j, and phi(u) = 0 for u <= 0, u^2 / (2 eta) up to eta, u - eta / 2 above: a sum over obstacles, not a minimum, zero beyond the
+        activation distance and C1 where it switches on.  All 8 links of a 7-DoF arm with at most 64 spheres, 32 obstacles and 1 024
+        pairs on full 64-row tiles: one kernel, a block of four wavefronts per tile; every other robot, size and tail one lane per row
+        (a walk outwards, the pairs, compute_external_torques' sweep inwards).  ``cost`` is DIFFERENTIABLE once with respect to q: its
+        backward is g[:, None] * dcost_dq and launches nothing; a second backward raises.  ``dcost_dq`` carries no history.  A row whose q
+        is not finite (or beyond 1e5) returns NaN and changes no bit of any other row.  A geometry with neither a world nor pairs raises
+        ValueError.  Argument handling: unbatched q gives unbatched results; CPU or HIP device; the current values of learnable links."""
+        unbatched, q, dw, T, ops_f = self._collision_args(q, geometry)
+        if not geometry.has_world and geometry.pairs is None:
+            raise ValueError("the geometry has neither a world nor self pairs: there is no cost")
+        params = (float(world_weight), float(world_activation), float(self_weight), float(self_activation))
+        for name, w, eta, on in (("world", params[0], params[1], geometry.has_world), ("self", params[2], params[3], geometry.pairs is not None)):
+            if on and not (math.isfinite(w) and w >= 0.0 and math.isfinite(eta) and eta > 0.0):
+                raise ValueError("%s_weight must be finite and >= 0 and %s_activation finite and > 0" % (name, name))
+        args = (dw.program, ops_f, dw.ops_i, T, self._n_dofs, geometry.tables(), params, bool(_composed))
+        if torch.is_grad_enabled() and q.requires_grad:
+            cost, dq = _CollisionCost.apply(q, *args)
+        else:
+            with torch.no_grad():
+                cost, dq = backend.collision_cost(args[0], args[1], args[2], q.detach(), *args[3:7], composed=args[7])
+        return CollisionCost(cost[0], dq[0]) if unbatched else CollisionCost(cost, dq)
+
+    def compute_sphere_distances(self, q: torch.Tensor, geometry: CollisionGeometry, *, _composed: bool = False) -> SphereDistances:
+        """The world centres of the geometry's spheres at q [B, n] and their clearances, in the CALLER's sphere order, from one launch
+        (csrc/drm_collision.hip drm_sphere_distances):
+            center          [B, S, 3]
+            world_distance  [B, S]  min over the obstacles of (signed distance of the centre - radius); +inf without a world
+            self_distance   [B, S]  min over the pairs the sphere is in of |x_i - x_j| - r_i - r_j; +inf when it is in none
+        A negative clearance is a penetration.  Forward only: a q that requires grad raises ValueError (compute_collision_cost is
+        the differentiable quantity; gradients of the clearances are out of scope).  Rows, devices, paths: compute_collision_cost's."""
+        unbatched, q, dw, T, ops_f = self._collision_args(q, geometry)
+        if torch.is_grad_enabled() and q.requires_grad:
+            raise ValueError("compute_sphere_distances is forward only: use compute_collision_cost for a differentiable quantity "
+                             "(or pass q.detach())")
+        with torch.no_grad():
+            outs = backend.sphere_distances(dw.program, ops_f, dw.ops_i, q.detach(), T, self._n_dofs, geometry.tables(),
+                                            composed=bool(_composed))
+            if geometry.order is not None:
+                outs = [x.index_select(1, geometry.order) for x in outs]
+        return SphereDistances(*[x[0] if unbatched else x for x in outs])
 
     # ------------------------------------------------------------------ plane contact and joint-limit springs
     def _contact_plan(self, contact, link_names, joint_limits):

@@ -784,6 +784,80 @@ int drm_contact_rollout(const drm_walk *dyn_walk, const drm_walk *links_walk, co
                         float *qd_traj, float *qdd_traj, float *scratch, void *stream);
 
 /*
+ * Collision: spheres fixed to the links against a world of spheres and oriented boxes shared by the whole batch, and against each
+ * other through a list of sphere pairs (additive to ABI 15).  One call gives the cost and its q-gradient (drm_collision_cost) or the
+ * sphere centres and their clearances (drm_sphere_distances).  The law (csrc/drm_collision.hpp), in float32 on explicit fused
+ * multiply-adds; x_s = p_l + R_l c_s the world centre of sphere s on link l, r_s its radius:
+ *   sphere obstacle (c, r)   sd = |x - c| - r, direction (x - c) / |x - c| (0 when the norm is 0)
+ *   box (c, Rb, h)           y = Rb^T (x - c), a = |y| - h; outside (max a > 0) sd = |max(a, 0)|, direction Rb (sign(y) max(a, 0) / sd);
+ *                            inside sd = max a, direction Rb (sign(y_i) e_i) with i the first index at which a is largest
+ *   d_sm = sd_m(x_s) - r_s                        d_ij = |x_i - x_j| - r_i - r_j
+ *   phi(u) = 0 (u <= 0), u^2 / (2 eta) (0 < u <= eta), u - eta / 2 (above); u = eta - d; phi' = clamp(u / eta, 0, 1)
+ *   cost = world_weight sum_{s, m} phi(world_activation - d_sm) + self_weight sum_pairs phi(self_activation - d_ij)
+ *   dq   = sum_l lin_jac_l^T F_l + ang_jac_l^T M_l,  F_l = sum_{s on l} dcost/dx_s,  M_l = sum_{s on l} (x_s - p_l) x dcost/dx_s
+ *   world_distance_s = min_m d_sm (+inf with an empty world)      self_distance_s = min over the pairs containing s (+inf without one)
+ * `links_walk` / n_targets: the many-target FK walk drm_link_motion takes.
+ *   drm_collision_spheres   spheres: DEVICE [S, 4] = centre in the STORED frame of the link's op (R~ = R P of DRM_OPI_PERM: c~ = P^T c; a
+ *                           link of two ops takes the frame of its last op) and radius, grouped by link: the root's group first (R = I,
+ *                           p = 0: a constant of the cost, nothing in dq, but they take part in pairs), then the targets in order.
+ *                           start: DEVICE [n_targets + 2] CSR offsets of the groups, start[0] = 0, start[n_targets + 1] = n_spheres;
+ *                           empty groups are allowed.
+ *   drm_collision_world     spheres: DEVICE [n_spheres, 4] = centre, radius; boxes: DEVICE [n_boxes, 16] = centre 3, half extents 3,
+ *                           rotation 9 row-major (box -> world), one pad.  Either may be empty.
+ *   drm_collision_pairs     pairs: DEVICE [n_pairs, 2] indices into the grouped sphere order, i != j.
+ *   drm_collision_cost      cost [B], dq [B, n]: either may be NULL, not both; with dq NULL no sweep inwards runs.  world or pairs may be
+ *                           NULL, not both.
+ *   drm_sphere_distances    center [B, S, 3], world_distance [B, S], self_distance [B, S] in the grouped order: any may be NULL, not
+ *                           all; an output whose input is NULL is filled with +inf.
+ * A links_walk that drm_link_motion runs fused (7-DoF arm chain of 8 ops, all 8 targets in walk order), full 64-row tiles, 16-byte
+ * aligned pointers, n_spheres <= 64, obstacles <= 32 and n_pairs <= 1 024: ONE launch, one row per lane, a block of wavefronts per
+ * 64-row tile that share the centres in LDS.  Everything else (trees, hands, prismatic and skew joints, link subsets, ragged tails,
+ * misaligned pointers, anything over the caps, DRM_LINKS_COMPOSED): one lane per row on the caller's stream out of the one scratch — a
+ * walk outwards with the world terms, the pairs, then drm_external_torques for dq.  Order of every sum: spheres in grouped order
+ * against the obstacles in table order, spheres before boxes, then the pairs in list order; the two paths agree to rounding.
+ * A row with a q that is not finite, or with a |q| beyond 1e5, is walked at q = 0, gets NaN in every output that is written and
+ * changes no bit of any other row.
+ *   scratch   the matching _scratch_floats query's floats over ALL B rows of the general path, whatever the alignment, the targets and
+ *             the caps: per row the centres (3 n_spheres), the link origins and wrenches (9 n_ops), the cost, plus the state of the
+ *             walk outwards and of drm_external_torques.  The _aligned form is for a call without DRM_LINKS_COMPOSED whose pointers
+ *             are all 16-byte aligned; told n_targets and the sizes of the tables (n_obstacles = world spheres + boxes), it returns
+ *             the floats of the B % 64 tail rows alone where the fused kernel takes the full tiles (which needs none: scratch may be
+ *             NULL when the query returns 0), and of all B rows otherwise.
+ * DRM_ERR_INVALID: a NULL required pointer, B < 0, an n_targets outside [1, n_ops], n_spheres < 1, a negative count, neither world nor
+ * pairs (drm_collision_cost), no output, an activation that is not finite and positive where its term is present, a weight that is
+ * negative or not finite; B == 0 returns DRM_OK.  Asynchronous on `stream`, no allocation, never a host synchronisation.
+ */
+typedef struct drm_collision_spheres {
+    const float *spheres;
+    const int32_t *start;
+    int32_t n_spheres;
+} drm_collision_spheres;
+typedef struct drm_collision_world {
+    const float *spheres;
+    const float *boxes;
+    int32_t n_spheres, n_boxes;
+} drm_collision_world;
+typedef struct drm_collision_pairs {
+    const int32_t *pairs;
+    int32_t n_pairs;
+} drm_collision_pairs;
+typedef struct drm_collision_params {
+    float world_weight, world_activation, self_weight, self_activation;
+} drm_collision_params;
+int64_t drm_collision_cost_scratch_floats(const drm_walk *links_walk, int64_t B, int32_t n_spheres);
+int64_t drm_collision_cost_scratch_floats_aligned(const drm_walk *links_walk, int64_t B, int32_t n_targets, int32_t n_spheres,
+                                                  int32_t n_obstacles, int32_t n_pairs);
+int64_t drm_sphere_distances_scratch_floats(const drm_walk *links_walk, int64_t B, int32_t n_spheres);
+int64_t drm_sphere_distances_scratch_floats_aligned(const drm_walk *links_walk, int64_t B, int32_t n_targets, int32_t n_spheres,
+                                                    int32_t n_obstacles, int32_t n_pairs);
+int drm_collision_cost(const drm_walk *links_walk, const float *q, int64_t B, int32_t n_targets, const drm_collision_spheres *spheres,
+                       const drm_collision_world *world, const drm_collision_pairs *pairs, const drm_collision_params *params,
+                       int32_t flags, float *cost, float *dq, float *scratch, void *stream);
+int drm_sphere_distances(const drm_walk *links_walk, const float *q, int64_t B, int32_t n_targets, const drm_collision_spheres *spheres,
+                         const drm_collision_world *world, const drm_collision_pairs *pairs, int32_t flags, float *center,
+                         float *world_distance, float *self_distance, float *scratch, void *stream);
+
+/*
  * Reverse-mode derivative of drm_fk: what torch autograd computes in the reference when a loss on
  * compute_forward_kinematics' outputs is back-propagated to q and to learnable `trans` / `rot_angles`
  * (robot_model.py:139-195, 223-248, 669-713; examples/learn_kinematics_of_iiwa.py:25-61).
