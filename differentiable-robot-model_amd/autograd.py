@@ -11,6 +11,8 @@ here one node per public method:
     _ForwardDynamics  compute_forward_dynamics (implicit differentiation)             drm_forward_dynamics / drm_rnea_backward
     _Energy           compute_energy (T, V and their gradients from ONE launch; first order only)          drm_energy
     _LinkAdjoint      compute_link_velocities / compute_external_torques (each the other's backward)       drm_link_motion, drm_external_torques, drm_link_power_dq
+    _ContactTorques   compute_contact_torques(differentiable=True)                    drm_contact_torques / drm_contact_torques_vjp
+    _ContactRollout   compute_contact_rollout(differentiable=True)                    drm_contact_rollout / a reverse sweep of per-step VJPs
     _FirstOrderOnly   marks the gradients of _FkMse computed under create_graph=True (differentiating through them raises)
     _GradLaunch       a first-order gradient launch as a differentiable node (create_graph=True: second derivatives with respect to
                       q / qd / qdd / f, the output cotangents and — round 6 — the walk's table, i.e. the learnable link parameters)
@@ -18,6 +20,8 @@ here one node per public method:
 plus the host-side maps between quaternion gradients and rotation-matrix adjoints (the reference's quaternion is assembled from
 the entries of R by a per-sample case rule, spatial_vector_algebra.py:108-136).  robot_model.py holds the model class only.
 """
+import types
+
 import torch
 
 from . import backend
@@ -808,3 +812,118 @@ class _LinkAdjoint(torch.autograd.Function):
         elif ctx.needs_input_grad[2]:
             ga = backend.external_torques(prog, ops_f, ops_i, q, grads[0], grads[1], n_targets, n_dofs, composed=composed).to(ctx.dtypes[0])
         return None, gq, ga, gb, None, None, None, None, None, None, None
+
+
+class _ContactFirstOrderOnly(_FirstOrderOnly):
+    """_FirstOrderOnly for the gradients of the contact nodes (_ContactTorques, _ContactRollout): correct to first order, they refuse to
+    be differentiated (the law is piecewise smooth and no second-order launch exists)."""
+
+    @staticmethod
+    def backward(ctx, _):
+        raise NotImplementedError(
+            "compute_contact_torques / compute_contact_rollout with differentiable=True are first-order nodes (their backward is the "
+            "drm_contact_torques_vjp launch, the branches of the forward taken): second derivatives through contact are out of scope")
+
+
+def _contact_first_order_only(grads):
+    with torch.enable_grad():
+        return [_ContactFirstOrderOnly.apply(g.requires_grad_(True)) if g is not None else None for g in grads]
+
+
+class _ContactTorques(torch.autograd.Function):
+    """(tau [B, n], force [B, T, 3], moment [B, T, 3]) of backend.contact_torques (csrc/drm_contact.hip) with a backward for tau:
+    (grad_q, grad_qd) = backend.contact_torques_vjp(q, qd, grad_tau) — ONE call, the branches of the law the forward took.  force
+    and moment are not differentiable.  First order only: under create_graph=True the gradients refuse a second differentiation
+    (_ContactFirstOrderOnly).  The walk's table, the plane, the radii and the springs are constants of the node: no history flows to
+    learnable link parameters or to the contact parameters."""
+
+    @staticmethod
+    def forward(ctx, q, qd, prog, ops_f, ops_i, n_targets, n_dofs, plane, radius, springs, composed):
+        ctx.dtypes = (q.dtype, qd.dtype)
+        q, qd = q.detach(), qd.detach()
+        tau, force, moment = backend.contact_torques(prog, ops_f, ops_i, q, qd, n_targets, n_dofs, plane, radius, springs, composed=composed)
+        ctx.save_for_backward(q, qd)
+        ctx.call = (prog, ops_f, ops_i, n_targets, n_dofs, plane, radius, springs, composed)
+        ctx.mark_non_differentiable(force, moment)
+        return tau, force, moment
+
+    @staticmethod
+    def backward(ctx, grad_tau, _f, _m):
+        q, qd = ctx.saved_tensors
+        prog, ops_f, ops_i, n_targets, n_dofs, plane, radius, springs, composed = ctx.call
+        want = tuple(name for name, need in zip(("grad_q", "grad_qd"), ctx.needs_input_grad[:2]) if need)
+        if not want:
+            return (None,) * 11
+        second = torch.is_grad_enabled()
+        with torch.no_grad():
+            gq, gqd = backend.contact_torques_vjp(prog, ops_f, ops_i, q, qd, grad_tau.to(torch.float32), n_targets, n_dofs, plane, radius,
+                                                  springs, want=want, composed=composed)
+        out = [gq.to(ctx.dtypes[0]) if gq is not None else None, gqd.to(ctx.dtypes[1]) if gqd is not None else None]
+        if second:
+            out = _contact_first_order_only(out)
+        return tuple(out) + (None,) * 9
+
+
+class _ContactRollout(torch.autograd.Function):
+    """backend.contact_rollout (csrc/drm_contact.hip) as ONE autograd node.  Forward: the rollout call, run with qdd_t kept.  Backward:
+    the reverse sweep of _ForwardDynamicsRollout with one addition per step — gtau_t = H^-1 A, the cotangent of the step's torques, is
+    also the cotangent of the step's contact and spring torques, so
+        (gq, gqd, gtau_t) = VJP_FD(q_t, qd_t, qdd_t; A)                          two launches (_ForwardDynamics._first_order)
+        (cq, cqd)         = backend.contact_torques_vjp(q_t, qd_t, gtau_t)        one call
+        Q += gq + cq,  V += gqd + cqd.
+    Gradients reach q0, qd0 and tau, first order only (_ContactFirstOrderOnly).  Both walks' tables, the plane, the radii and the
+    springs are constants of the node: NO gradient reaches learnable link parameters (a gradient through the dynamics alone would
+    leave out the contact links' share and be wrong) or the contact parameters.  qdd, when asked for, is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, q0, qd0, tau, dyn, links, vjp_links, dt, gravity, damping, explicit, n_targets, n_dofs, plane, radius, springs, want_qdd,
+                composed):
+        ctx.dtypes = (q0.dtype, qd0.dtype, tau.dtype)
+        q0, qd0 = q0.detach(), qd0.detach()
+        q_traj, qd_traj, qdd_traj = backend.contact_rollout(dyn, links, q0, qd0, tau.detach(), dt, gravity, damping, explicit, n_targets, n_dofs,
+                                                            plane, radius, springs, want_qdd=True, composed=composed)
+        ctx.save_for_backward(q0, qd0, q_traj, qd_traj, qdd_traj)
+        ctx.call = (dyn, vjp_links, float(dt), (gravity, damping), explicit, n_targets, n_dofs, plane, radius, springs, composed)
+        if not want_qdd:
+            return q_traj, qd_traj, None
+        qdd_out = qdd_traj.clone()
+        ctx.mark_non_differentiable(qdd_out)
+        return q_traj, qd_traj, qdd_out
+
+    @staticmethod
+    def backward(ctx, grad_q_traj, grad_qd_traj, _qdd):
+        q0, qd0, q_traj, qd_traj, qdd_traj = ctx.saved_tensors
+        dyn, links, dt, flags, explicit, n_targets, n, plane, radius, springs, composed = ctx.call
+        second = torch.is_grad_enabled()
+        T, B = q_traj.shape[0], q_traj.shape[1]
+        walk = types.SimpleNamespace(program=dyn[0], ops_i=dyn[2])      # (what _ForwardDynamics._first_order reads of a dynamics walk)
+        lprog, lops_f, lops_i = links      # (``vjp_links``: the contact links' walk; without a plane any links walk, it is not walked)
+        with torch.no_grad():
+            table = dyn[1].detach()
+            Q = torch.zeros(B, n, device=q_traj.device, dtype=torch.float32)
+            V = torch.zeros_like(Q)
+            gtau = torch.empty(T, B, n, device=q_traj.device, dtype=torch.float32)
+            for t in range(T - 1, -1, -1):
+                if grad_q_traj is not None:
+                    Q = Q + grad_q_traj[t].to(torch.float32)
+                if grad_qd_traj is not None:
+                    V = V + grad_qd_traj[t].to(torch.float32)
+                if explicit:
+                    A = dt * V
+                    V = V + dt * Q
+                else:
+                    V = V + dt * Q
+                    A = dt * V
+                q_t = q0.to(torch.float32) if t == 0 else q_traj[t - 1]
+                qd_t = qd0.to(torch.float32) if t == 0 else qd_traj[t - 1]
+                gq, gqd, gtau_t, _ = _ForwardDynamics._first_order(walk, n, flags, q_t, qd_t, qdd_traj[t], table, A, True, 0)
+                cq, cqd = backend.contact_torques_vjp(lprog, lops_f, lops_i, q_t, qd_t, gtau_t, n_targets, n, plane, radius, springs,
+                                                      composed=composed)
+                Q = (Q + gq) + cq
+                V = (V + gqd) + cqd
+                gtau[t] = gtau_t
+        out = [Q.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None, V.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None,
+               gtau.to(ctx.dtypes[2]) if ctx.needs_input_grad[2] else None]
+        if second:
+            out = _contact_first_order_only(out)
+        return tuple(out) + (None,) * 14

@@ -137,6 +137,7 @@ EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "dr
            "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
            "drm_link_power_dq", "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
            "drm_contact_torques", "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
+           "drm_contact_torques_vjp", "drm_contact_torques_vjp_scratch_floats", "drm_contact_torques_vjp_scratch_floats_aligned",
            "drm_contact_rollout", "drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned",
            "drm_collision_cost", "drm_collision_cost_scratch_floats", "drm_collision_cost_scratch_floats_aligned",
            "drm_sphere_distances", "drm_sphere_distances_scratch_floats", "drm_sphere_distances_scratch_floats_aligned")
@@ -243,7 +244,8 @@ def load_library(path: str = None, kind: str = "cuda"):
                      "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
                      "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
                      "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
-                     "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned"):
+                     "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
+                     "drm_contact_torques_vjp_scratch_floats", "drm_contact_torques_vjp_scratch_floats_aligned"):
             getattr(lib, name).restype = i64
             getattr(lib, name).argtypes = [wp, i64]
         for name in ("drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned"):
@@ -252,6 +254,8 @@ def load_library(path: str = None, kind: str = "cuda"):
         pp, sp = ctypes.POINTER(DrmContactPlane), ctypes.POINTER(DrmJointSprings)
         lib.drm_contact_torques.restype = ctypes.c_int
         lib.drm_contact_torques.argtypes = [wp, vp, vp, i64, i32, pp, vp, sp, vp, vp, i32, vp, vp, vp, vp, vp]
+        lib.drm_contact_torques_vjp.restype = ctypes.c_int
+        lib.drm_contact_torques_vjp.argtypes = [wp, vp, vp, vp, i64, i32, pp, vp, sp, vp, vp, i32, vp, vp, vp, vp]
         lib.drm_contact_rollout.restype = ctypes.c_int
         lib.drm_contact_rollout.argtypes = [wp, wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, i32, pp, vp, sp, vp, vp, vp, vp, vp, vp, vp]
         for name in ("drm_collision_cost_scratch_floats", "drm_sphere_distances_scratch_floats"):
@@ -1350,6 +1354,39 @@ def contact_torques(prog: WalkProgram, ops_f, ops_i, q, qd, n_targets: int, n_do
                                        LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(force), ptr(moment), ptr(scratch),
                                        _stream(q.device)), lib)
     return tau, force, moment
+
+
+def contact_torques_vjp(prog: WalkProgram, ops_f, ops_i, q, qd, grad_tau, n_targets: int, n_dofs: int, plane, radius=None, springs=None,
+                        want=("grad_q", "grad_qd"), composed: bool = False):
+    """(grad_q [B, n], grad_qd [B, n]): the vector-Jacobian product of contact_torques' tau under the cotangent ``grad_tau`` [B, n]
+    (include/drm_hip.h drm_contact_torques_vjp).  ``want`` names the outputs to compute, the other comes back as None.  ``plane``
+    may be None when ``springs`` are given (the springs' share alone).  ``plane`` / ``radius`` / ``springs``: _contact_structs.
+    ``composed``: as for link_motion."""
+    lib = _lib_of(q, "q", ops_f)
+    q, qd, grad_tau = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(grad_tau, "grad_tau", n_dofs)
+    B = int(q.shape[0])
+    if qd.shape[0] != B or grad_tau.shape[0] != B:
+        raise ValueError("q / qd / grad_tau batch sizes differ")
+    if plane is None and springs is None:
+        raise ValueError("contact_torques_vjp needs a plane or springs")
+    want = tuple(want)
+    if not want or any(w not in ("grad_q", "grad_qd") for w in want):
+        raise ValueError("want must name at least one of ('grad_q', 'grad_qd')")
+    pl, radius, sp, lower, upper = _contact_structs(plane, radius, springs, n_targets, n_dofs, q.device)
+    made = dict(zip(want, _outputs(q.device, *[(B, n_dofs)] * len(want))))
+    grad_q, grad_qd = made.get("grad_q"), made.get("grad_qd")
+    if B == 0:
+        return grad_q, grad_qd
+    composed = _links_composed(composed)
+    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    scratch = _scratch(lib, "drm_contact_torques_vjp", (walk,), B, composed, q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ref = lambda st: ctypes.byref(st) if st is not None else None
+    with _on_device(q.device):
+        _check(lib.drm_contact_torques_vjp(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), grad_tau.data_ptr(), B, n_targets, ref(pl),
+                                           ptr(radius), ref(sp), ptr(lower), ptr(upper), LINKS_COMPOSED if composed else 0, ptr(grad_q),
+                                           ptr(grad_qd), ptr(scratch), _stream(q.device)), lib)
+    return grad_q, grad_qd
 
 
 def _collision_structs(tables, device):

@@ -9,6 +9,11 @@
 //                                chain_trig, ONE sweep outwards with velocities that keeps the origins and axes, the law per link, one
 //                                sweep inwards, the springs (drm_contact.hpp contact_chain_torques).  The [64, 7] tile of torques and,
 //                                when asked for, the two [64, 8, 3] wrench tiles leave through LDS in 16-byte stores.
+//   contact_torques_vjp_arm_kernel   drm_contact_torques_vjp under contact_torques_arm_kernel's condition: the cotangent of the
+//                                torques beside q and qd (84 B in per row), ONE chain_trig, ONE sweep outwards that carries the
+//                                velocities at rates qd and at rates grad_tau together with the law and its backward per link, ONE
+//                                sweep inwards with three wrench sets and two free vectors, the springs (drm_contact.hpp
+//                                contact_chain_torques_vjp); the two [64, 7] tiles leave through LDS in 16-byte stores (56 B out).
 //   contact_rollout_arm_kernel   the same walks with a dynamics walk drm_rollout.hip's arm kernel takes, B n % 4 == 0: that kernel's
 //                                body with the contact and spring torques added to the right-hand side before the solve.  BOTH
 //                                constant tables staged in LDS once for all T steps; plane, radii, springs and bounds are wave-uniform
@@ -20,16 +25,24 @@
 //                                contact_add_kernel (the springs, and tau[t] in a rollout); per rollout step then
 //                                drm_forward_dynamics and contact_rollout_integrate_kernel.  This is the second of the two forms
 //                                the general drm_contact_torques may take: it adds no tree walk of its own to the ones drm_links.hip
-//                                already holds to fp64.
+//                                already holds to fp64.  The VJP composes likewise: drm_link_motion at (q, qd) and at (q, grad_tau)
+//                                -> contact_law_vjp_kernel -> drm_link_power_dq twice and drm_external_torques once ->
+//                                contact_vjp_add_kernel (the sums, the springs' share, NaN rows).
 //
 // Compiler's kernel-resource-usage remarks (gfx950, the flags of this unit; profiles/contact_resource_usage.txt):
 //   contact_torques_arm_kernel<8, 7, 8>      VGPRs 126  spills 0  LDS 15 616 B  occupancy 3 waves / SIMD
+//   contact_torques_vjp_arm_kernel<8, 7, 8>  VGPRs 256 + 21 AGPRs  spills 0  scratch 0  LDS 4 608 B  occupancy 1 wave / SIMD
 //   contact_rollout_arm_kernel<8, 7, 7>      VGPRs 224  spills 0  LDS 51 200 B  occupancy 2 waves / SIMD
 //   contact_rollout_arm_kernel<8, 7, 8>      VGPRs 240  spills 0  LDS 57 344 B  occupancy 2 waves / SIMD
 // (forward_dynamics_rollout_arm_kernel: 200 / 206 VGPRs, 2 waves per SIMD: the contact phase costs 24 / 34 registers and no wave.)
+// The VJP kernel keeps the per-link records of its sweep inwards (origins, axes, two velocity sets, f, gv and the depth cotangent; m, gw
+// and gp are formed again on the way in) in registers at one wavefront per SIMD.  Parking the two velocity sets in LDS (72 floats per
+// row, 19 456 B per wavefront) and asking for two wavefronts per SIMD (amdgpu_waves_per_eu) was compiled and NOT kept: the register
+// allocator still spilled 21 - 25 VGPRs to scratch at 256, with or without the parking — the pressure peaks inside the unrolled sweep
+// outwards, not in the records — and scratch is what the kernel must not have.
 //
 // Per row and step, fused rollout: in tau [n], out q, qd [n] (84 B; 112 B with qdd_traj), as the plain rollout.  Torques, fused:
-// 56 B in, 28 B out (220 B with both wrench tiles).
+// 56 B in, 28 B out (220 B with both wrench tiles); their VJP, fused: 84 B in, 56 B out.
 #include <math.h>
 
 #include "drm_common.hpp"
@@ -120,6 +133,63 @@ __global__ void __launch_bounds__(WAVE)
     tile_store<NJ>(tau + b0 * NJ, WAVE, NJ, 0u, lt, lane, true);
     if (force) tile_store<S>(force + b0 * S, WAVE, S, contact_tile_magic(S), lf, lane, false, true);
     if (moment) tile_store<S>(moment + b0 * S, WAVE, S, contact_tile_magic(S), lm, lane, false, true);
+}
+
+// drm_contact_torques_vjp, fused: contact_torques_arm_kernel's tiles and LDS image with the cotangent lam of the torques beside q and qd
+// (84 B in per row), drm_contact.hpp contact_chain_torques_vjp per lane, the springs' share, and the two [64, 7] tiles of grad_q and
+// grad_qd out through LDS in 16-byte stores (56 B out per row).  The per-link records of the sweep inwards stay in registers, at one
+// wavefront per SIMD (the file header says what else was compiled).
+template <int CAP, int NJ, int LINKS>
+__global__ void __launch_bounds__(WAVE)
+    contact_torques_vjp_arm_kernel(const float *__restrict__ ops_f, const float *__restrict__ q, const float *__restrict__ qd,
+                                   const float *__restrict__ lam, int n_tiles, ContactPlane pl, const float *__restrict__ radius,
+                                   SpringArgs sp, float *__restrict__ grad_q, float *__restrict__ grad_qd) {
+    static_assert(NJ & 1, "odd row widths only (linear LDS image)");
+    static_assert(CAP * DRM_OPF_STRIDE == 4 * WAVE, "one float4 per lane copies the constant table");
+    constexpr int C_FLOATS = CAP * DRM_OPF_STRIDE, Q_FLOATS = round4(WAVE * NJ);
+    __shared__ __attribute__((aligned(16))) float smem[C_FLOATS + 2 * Q_FLOATS];
+    const int tile = (int)blockIdx.x;
+    if (tile >= n_tiles) return;
+    const unsigned lane = threadIdx.x & 63u;
+    float *lc = smem, *lgq = smem + C_FLOATS, *lgqd = lgq + Q_FLOATS;
+    const int64_t b0 = (int64_t)tile * WAVE;
+
+    float4 cv = reinterpret_cast<const float4 *>(ops_f)[lane];
+    float qv[NJ], qdv[NJ], lv[NJ];
+    {
+        const int64_t r0 = (b0 + lane) * NJ;
+#pragma unroll
+        for (int d = 0; d < NJ; ++d) qv[d] = q[r0 + d];
+#pragma unroll
+        for (int d = 0; d < NJ; ++d) qdv[d] = qd[r0 + d];
+#pragma unroll
+        for (int d = 0; d < NJ; ++d) lv[d] = lam[r0 + d];
+    }
+    pin(cv);
+    reinterpret_cast<float4 *>(lc)[lane] = cv;
+    wave_lds_sync();
+    auto row = [&](int k) -> const float * { return lc + k * DRM_OPF_STRIDE; };
+
+    bool bad = false;
+#pragma unroll
+    for (int d = 0; d < NJ; ++d) bad = bad || lag_bad_input(qv[d], qdv[d]) || !(fabsf(lv[d]) <= 3.0e38f);
+#pragma unroll
+    for (int d = 0; d < NJ; ++d) { qv[d] = bad ? 0.0f : qv[d]; qdv[d] = bad ? 0.0f : qdv[d]; lv[d] = bad ? 0.0f : lv[d]; }
+    const float nan = __builtin_nanf("");
+
+    float gq[NJ], gqd[NJ], cs[NJ], sn[NJ];
+    chain_trig<NJ>(qv, cs, sn);
+    contact_chain_torques_vjp<LINKS, NJ>(
+        row, pl, cs, sn, qdv, lv, [&](int k) { return radius ? radius[k] : 0.0f; }, [&](int j, float a, float b) { gq[j] = a; gqd[j] = b; });
+    if (sp.on) {
+#pragma unroll
+        for (int d = 0; d < NJ; ++d) joint_spring_vjp(sp.k, sp.c, sp.lower[d], sp.upper[d], qv[d], lv[d], gq[d], gqd[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < NJ; ++d) { lgq[lane * NJ + d] = bad ? nan : gq[d]; lgqd[lane * NJ + d] = bad ? nan : gqd[d]; }
+    wave_lds_sync();
+    if (grad_q) tile_store<NJ>(grad_q + b0 * NJ, WAVE, NJ, 0u, lgq, lane, true);
+    if (grad_qd) tile_store<NJ>(grad_qd + b0 * NJ, WAVE, NJ, 0u, lgqd, lane, true);
 }
 
 // forward_dynamics_rollout_arm_kernel (drm_rollout.hip) with the contact and spring torques of the step's state added to the
@@ -273,6 +343,48 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// The composed path's law and its backward: one thread per (row, link).  (a, b): the links' velocities at rates lam, the cotangents of
+// the wrenches.  Rows that cannot be used are seen to by contact_vjp_add_kernel.
+__global__ void __launch_bounds__(256)
+    contact_law_vjp_kernel(const float *__restrict__ pos, const float *__restrict__ lin_vel, const float *__restrict__ ang_vel,
+                           const float *__restrict__ lin_cot, const float *__restrict__ ang_cot, int64_t count, int T, ContactPlane pl,
+                           const float *__restrict__ radius, float *__restrict__ force, float *__restrict__ moment, float *__restrict__ gpos,
+                           float *__restrict__ glin, float *__restrict__ gang) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+        const int t = (int)(i % T);
+        float p[3], v[3], w[3], a[3], b[3], f[3], m[3], gp[3], gv[3], gw[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p[k] = pos[3 * i + k]; v[k] = lin_vel[3 * i + k]; w[k] = ang_vel[3 * i + k]; a[k] = lin_cot[3 * i + k]; b[k] = ang_cot[3 * i + k];
+        }
+        contact_wrench_vjp(pl, radius ? radius[t] : 0.0f, p, v, w, a, b, f, m, gp, gv, gw);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            force[3 * i + k] = f[k]; moment[3 * i + k] = m[k]; gpos[3 * i + k] = gp[k]; glin[3 * i + k] = gv[k]; gang[3 * i + k] = gw[k];
+        }
+    }
+}
+
+// grad_q = (dq1 + t2) + dq3 + the springs' share, grad_qd = tau3 + the springs' share, element-wise over count = rows * n coordinates
+// (the four inputs NULL: no plane).  A coordinate of a row with a q, qd or lam that cannot be used is NaN.
+__global__ void __launch_bounds__(256)
+    contact_vjp_add_kernel(const float *__restrict__ dq1, const float *__restrict__ t2, const float *__restrict__ dq3,
+                           const float *__restrict__ tau3, const float *__restrict__ q, const float *__restrict__ qd,
+                           const float *__restrict__ lam, int64_t count, int n, SpringArgs sp, float *__restrict__ grad_q,
+                           float *__restrict__ grad_qd) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+        const int d = (int)(i % n);
+        float gq = dq1 ? (dq1[i] + t2[i]) + dq3[i] : 0.0f, gqd = dq1 ? tau3[i] : 0.0f;
+        if (sp.on) joint_spring_vjp(sp.k, sp.c, sp.lower[d], sp.upper[d], q[i], lam[i], gq, gqd);
+        const int64_t r0 = i - d;
+        bool bad = false;
+        for (int j = 0; j < n; ++j) bad = bad || lag_bad_input(q[r0 + j], qd[r0 + j]) || !(fabsf(lam[r0 + j]) <= 3.0e38f);
+        if (bad) gq = gqd = __builtin_nanf("");
+        if (grad_q) grad_q[i] = gq;
+        if (grad_qd) grad_qd[i] = gqd;
+    }
+}
+
 // the composed path's integrator (drm_rollout.hip's, which a launch from this unit cannot reach): one step of count coordinates.
 // qdd_out (NULL: not wanted) gets a copy of the accelerations: drm_forward_dynamics always writes them to the scratch, so that the
 // kernel it picks by the alignment of its pointers, and with it every bit of q and qd, does not depend on whether qdd_traj is asked for
@@ -404,6 +516,83 @@ extern "C" int drm_contact_torques(const drm_walk *lw, const float *q, const flo
     float *sub = scratch ? scratch + contact_buf_floats(rows, T, n) : nullptr;
     return contact_composed(lw, a, q + lo * n, qd + lo * n, nullptr, rows, T, n, flags, 1, tau + lo * n, force ? force + lo * T * 3 : nullptr,
                             moment ? moment + lo * T * 3 : nullptr, scratch, sub, s);
+}
+
+// The composed vector-Jacobian product of `rows` rows.  `buf`: 10 x r4(rows T 3) (the links' motion at rates qd, their velocities at
+// rates lam, the wrenches and the three cotangents of the law) + 4 x r4(rows n) floats; `sub`: the scratch of the link calls.
+static int64_t contact_vjp_buf_floats(int64_t rows, int T, int n) { return 10 * r4(rows * T * 3) + 4 * r4(rows * n); }
+static int64_t contact_vjp_links_sub(const drm_walk *lw, int64_t B) {
+    const int64_t a = contact_links_sub(lw, B), b = drm_link_power_dq_scratch_floats(lw, B);
+    return r4(a > b ? a : b);
+}
+static int contact_vjp_composed(const drm_walk *lw, const ContactArgs &a, const float *q, const float *qd, const float *lam, int64_t rows,
+                                int T, int n, int flags, float *grad_q, float *grad_qd, float *buf, float *sub, hipStream_t s) {
+    const int64_t count = rows * n;
+    const float *dq1 = nullptr, *t2 = nullptr, *dq3 = nullptr, *tau3 = nullptr;
+    if (a.has_plane) {
+        if (!buf) return fail(DRM_ERR_INVALID, "pass the matching _scratch_floats() query's floats of scratch");
+        const int64_t L = r4(rows * T * 3), N = r4(count);
+        float *pos = buf, *lv = pos + L, *av = lv + L, *la = av + L, *lb = la + L, *f = lb + L, *m = f + L, *gp = m + L, *gv = gp + L;
+        float *gw = gv + L, *o1 = gw + L, *o2 = o1 + N, *o3 = o2 + N, *o4 = o3 + N;
+        const int lf = flags & DRM_LINKS_COMPOSED;
+        int rc = drm_link_motion(lw, q, qd, nullptr, rows, T, lf, pos, lv, av, nullptr, nullptr, sub, s);
+        if (rc) return rc;
+        rc = drm_link_motion(lw, q, lam, nullptr, rows, T, lf, nullptr, la, lb, nullptr, nullptr, sub, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(contact_law_vjp_kernel, dim3(contact_blocks(rows * T)), dim3(256), 0, s, (const float *)pos, (const float *)lv,
+                           (const float *)av, (const float *)la, (const float *)lb, rows * T, T, a.pl, a.radius, f, m, gp, gv, gw);
+        rc = launched();
+        if (rc) return rc;
+        rc = drm_link_power_dq(lw, q, lam, f, m, rows, T, lf, o1, nullptr, sub, s);
+        if (rc) return rc;
+        rc = drm_external_torques(lw, q, gp, nullptr, rows, T, lf, o2, sub, s);
+        if (rc) return rc;
+        rc = drm_link_power_dq(lw, q, qd, gv, gw, rows, T, lf, o3, o4, sub, s);
+        if (rc) return rc;
+        dq1 = o1; t2 = o2; dq3 = o3; tau3 = o4;
+    }
+    hipLaunchKernelGGL(contact_vjp_add_kernel, dim3(contact_blocks(count)), dim3(256), 0, s, dq1, t2, dq3, tau3, q, qd, lam, count, n, a.sp,
+                       grad_q, grad_qd);
+    return launched();
+}
+
+// The composed form over ALL B rows, as drm_contact_torques_scratch_floats.
+extern "C" int64_t drm_contact_torques_vjp_scratch_floats(const drm_walk *lw, int64_t B) {
+    if (rows_check_walk(lw) || B <= 0) return 0;
+    return contact_vjp_buf_floats(B, lw->n_ops, lw->n_dofs) + contact_vjp_links_sub(lw, B);
+}
+extern "C" int64_t drm_contact_torques_vjp_scratch_floats_aligned(const drm_walk *lw, int64_t B) {
+    return drm_contact_torques_vjp_scratch_floats(lw, B);
+}
+
+extern "C" int drm_contact_torques_vjp(const drm_walk *lw, const float *q, const float *qd, const float *grad_tau, int64_t B,
+                                       int32_t n_targets, const drm_contact_plane *plane, const float *radius,
+                                       const drm_joint_springs *springs, const float *lower, const float *upper, int32_t flags,
+                                       float *grad_q, float *grad_qd, float *scratch, void *stream) {
+    int rc = rows_check_walk(lw);
+    if (rc) return rc;
+    if (!q || !qd || !grad_tau) return fail(DRM_ERR_INVALID, "q / qd / grad_tau must not be NULL");
+    if (!grad_q && !grad_qd) return fail(DRM_ERR_INVALID, "grad_q and grad_qd are both NULL");
+    ContactArgs a;
+    rc = contact_check(lw, B, n_targets, plane, radius, springs, lower, upper, a);
+    if (rc) return rc;
+    if (B == 0) return DRM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int n = lw->n_dofs, T = n_targets;
+    int64_t lo = 0;
+    if (plane && contact_links_fused(lw, T, B, flags, aligned16(q, qd, grad_tau, grad_q, grad_qd))) {
+        const int n_tiles = (int)(B / WAVE);
+        hipLaunchKernelGGL((contact_torques_vjp_arm_kernel<8, 7, 8>), dim3((unsigned)n_tiles), dim3(WAVE), 0, s, lw->ops_f, q, qd, grad_tau,
+                           n_tiles, a.pl, a.radius, a.sp, grad_q, grad_qd);
+        rc = launched();
+        if (rc) return rc;
+        lo = (int64_t)n_tiles * WAVE;
+        if (lo == B) return DRM_OK;
+    }
+    const int64_t rows = B - lo;
+    float *sub = scratch ? scratch + contact_vjp_buf_floats(rows, T, n) : nullptr;
+    return contact_vjp_composed(lw, a, q + lo * n, qd + lo * n, grad_tau + lo * n, rows, T, n, flags, grad_q ? grad_q + lo * n : nullptr,
+                                grad_qd ? grad_qd + lo * n : nullptr, scratch, sub, s);
 }
 
 // both walks, the batch and every pointer qualify for contact_rollout_arm_kernel

@@ -554,6 +554,55 @@ void contact_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q,
         }
     }
 }
+// drm_contact_torques_vjp of `rows` rows from q, qd, lam on (grad_q or grad_qd may be NULL): the chain form where drm_contact.hip would
+// launch its fused kernel, elsewhere its composition of the link sweeps, the law's backward and the q-gradients of the sweeps.
+void contact_vjp_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q, const float *qd, const float *lam, int64_t rows, int T,
+                           int n, int flags, float *grad_q, float *grad_qd) {
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const size_t N = (size_t)rows * n;
+    std::vector<float> gq(N, 0.0f), gqd(N, 0.0f);
+    auto row_bad = [&](int64_t b) {
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::lag_bad_input(q[b * n + d], qd[b * n + d]) || !(std::fabs(lam[b * n + d]) <= 3.0e38f);
+        return bad;
+    };
+    if (a.has_plane && links_chain_walk(lw, T, flags)) {
+        auto row = [&](int k) { return lw->ops_f + k * DRM_OPF_STRIDE; };
+        for (int64_t b = 0; b < rows; ++b) {
+            const bool bad = row_bad(b);
+            float qv[7], qdv[7], lv[7], cs[7], sn[7];
+            for (int d = 0; d < 7; ++d) {
+                qv[d] = bad ? 0.0f : q[b * 7 + d]; qdv[d] = bad ? 0.0f : qd[b * 7 + d]; lv[d] = bad ? 0.0f : lam[b * 7 + d];
+            }
+            drm::chain_trig<7>(qv, cs, sn);
+            drm::contact_chain_torques_vjp<8, 7>(
+                row, a.pl, cs, sn, qdv, lv, [&](int k) { return a.radius ? a.radius[k] : 0.0f; },
+                [&](int j, float x, float y) { gq[b * 7 + j] = x; gqd[b * 7 + j] = y; });
+        }
+    } else if (a.has_plane) {
+        const size_t L = (size_t)rows * T * 3;
+        std::vector<float> pos(L), lv(L), av(L), la(L), lb(L), f(L), m(L), gp(L), gv(L), gw(L), o1(N), o2(N), o3(N);
+        link_motion_host_rows<1>(lw, q, qd, nullptr, 0, rows, T, flags, pos.data(), lv.data(), av.data(), nullptr, nullptr);
+        link_motion_host_rows<1>(lw, q, lam, nullptr, 0, rows, T, flags, nullptr, la.data(), lb.data(), nullptr, nullptr);
+        for (int64_t i = 0; i < rows * T; ++i)
+            drm::contact_wrench_vjp(a.pl, a.radius ? a.radius[i % T] : 0.0f, &pos[3 * i], &lv[3 * i], &av[3 * i], &la[3 * i], &lb[3 * i],
+                                    &f[3 * i], &m[3 * i], &gp[3 * i], &gv[3 * i], &gw[3 * i]);
+        link_power_dq_host_rows(lw, q, lam, f.data(), m.data(), 0, rows, T, flags, o1.data(), nullptr);
+        link_torques_host_rows(lw, q, gp.data(), nullptr, 0, rows, T, flags, o2.data());
+        link_power_dq_host_rows(lw, q, qd, gv.data(), gw.data(), 0, rows, T, flags, o3.data(), gqd.data());
+        for (size_t i = 0; i < N; ++i) gq[i] = (o1[i] + o2[i]) + o3[i];
+    }
+    for (int64_t b = 0; b < rows; ++b) {
+        const bool bad = row_bad(b);
+        for (int d = 0; d < n; ++d) {
+            const int64_t i = b * n + d;
+            float x = gq[i], y = gqd[i];
+            if (a.lower) drm::joint_spring_vjp(a.k, a.c, a.lower[d], a.upper[d], q[i], lam[i], x, y);
+            if (grad_q) grad_q[i] = bad ? nan : x;
+            if (grad_qd) grad_qd[i] = bad ? nan : y;
+        }
+    }
+}
 // what drm_collision_cost and drm_sphere_distances ask of their arguments (drm_collision.hip coll_check)
 int collision_check(const drm_walk *w, const float *q, int64_t B, int T, const drm_collision_spheres *spheres, const drm_collision_world *world,
                     const drm_collision_pairs *pairs, drm::CollTables &t) {
@@ -979,6 +1028,24 @@ int drm_contact_torques(const drm_walk *lw, const float *q, const float *qd, int
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         contact_host_rows(lw, a, q + b0 * n, qd + b0 * n, nullptr, rows, T, n, flags, true, tau + b0 * n,
                           force ? force + b0 * T * 3 : nullptr, moment ? moment + b0 * T * 3 : nullptr);
+    });
+    return DRM_OK;
+}
+
+int64_t drm_contact_torques_vjp_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_contact_torques_vjp_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+int drm_contact_torques_vjp(const drm_walk *lw, const float *q, const float *qd, const float *grad_tau, int64_t B, int32_t T,
+                            const drm_contact_plane *plane, const float *radius, const drm_joint_springs *springs, const float *lower,
+                            const float *upper, int32_t flags, float *grad_q, float *grad_qd, float *, void *) {
+    if (int rc = check_sweep_walk(lw)) return rc;
+    if (!q || !qd || !grad_tau) return fail(DRM_ERR_INVALID, "q / qd / grad_tau must not be NULL");
+    if (!grad_q && !grad_qd) return fail(DRM_ERR_INVALID, "grad_q and grad_qd are both NULL");
+    ContactArgs a;
+    if (int rc = contact_check(lw, B, T, plane, radius, springs, lower, upper, a)) return rc;
+    const int n = lw->n_dofs;
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        contact_vjp_host_rows(lw, a, q + b0 * n, qd + b0 * n, grad_tau + b0 * n, rows, T, n, flags, grad_q ? grad_q + b0 * n : nullptr,
+                              grad_qd ? grad_qd + b0 * n : nullptr);
     });
     return DRM_OK;
 }

@@ -27,7 +27,8 @@ from . import backend
 from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, OPI_OUT, OPI_PERM, _PERM, RobotSpec, WalkProgram, build_robot_spec,
                       build_walk, fold_link_table, foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
-                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _CollisionCost, _quat_grad_to_rot)
+                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _CollisionCost, _ContactTorques, _ContactRollout,
+                       _quat_grad_to_rot)
 from .rigid_body import DifferentiableRigidBody, LinkPose, LinkVelocity
 from .urdf_utils import URDFRobotModel
 
@@ -2389,7 +2390,8 @@ class DifferentiableRobotModel(torch.nn.Module):
                     raise ValueError("%s is forward only: it has no gradient with respect to %s (pass %s.detach())" % (what, name, name))
 
     def compute_contact_torques(self, q: torch.Tensor, qd: torch.Tensor, contact: PlaneContact, link_names: Optional[List[str]] = None,
-                                joint_limits: Optional[JointLimitSprings] = None, *, _composed: bool = False) -> ContactTorques:
+                                joint_limits: Optional[JointLimitSprings] = None, *, differentiable: bool = False,
+                                _composed: bool = False) -> ContactTorques:
         """The joint torques of a plane's penalty contact with spheres on the named links (None: every link in get_link_names()
         order) at q, qd [B, n], plus those of joint-limit springs when ``joint_limits`` is given, and the wrenches themselves:
             tau     [B, n]     sum_l lin_jac_l^T force_l + ang_jac_l^T moment_l (+ tau_lim)
@@ -2397,27 +2399,67 @@ class DifferentiableRobotModel(torch.nn.Module):
         The law is PlaneContact's; ``link_names`` is handled as in compute_link_motion (any order, repeats, the root — which never
         touches and gets zeros).  ONE kernel launch for all 8 links of a 7-DoF arm on full 64-row tiles (csrc/drm_contact.hip: one
         sweep outwards with velocities, the law per link, one sweep inwards, all in registers); every other robot and link set
-        composes the link-motion launch, one element-wise law kernel, the external-torques launch and one add.  Forward only: a q
-        or qd that requires grad raises ValueError, and the results carry no autograd history (the current values of learnable
-        links are used).  A row whose q or qd is not finite returns NaN and changes no bit of any other row."""
+        composes the link-motion launch, one element-wise law kernel, the external-torques launch and one add.  By default forward
+        only: a q or qd that requires grad raises ValueError, and the results carry no autograd history (the current values of
+        learnable links are used).  ``differentiable=True`` opts in: the forward values are the same bits from the same launch, and
+        ``tau`` is DIFFERENTIABLE once with respect to q and qd — its backward is ONE compute_contact_torques_vjp call
+        (autograd._ContactTorques; a second backward raises NotImplementedError).  The law is piecewise smooth: at a switch the
+        gradient is that of the branch the forward took.  ``force`` and ``moment`` come back detached, and no gradient reaches
+        learnable link parameters or the contact parameters: the walk's table is a constant of the node.  A row whose q or qd is not
+        finite returns NaN and changes no bit of any other row."""
         if contact is None:
             raise ValueError("compute_contact_torques needs a PlaneContact")
         unbatched, q, (qd,) = self._links_args(q, [(qd, "qd")], (self._n_dofs,))
         assert qd is not None, "qd must be given"
-        self._refuse_grad("compute_contact_torques", q=q, qd=qd)
+        if not differentiable:
+            self._refuse_grad("compute_contact_torques", q=q, qd=qd)
         self._require_device()
         with torch.no_grad():
             lw, T, sel, identity, plane, radius, springs = self._contact_plan(contact, link_names, joint_limits)
-            tau, force, moment = backend.contact_torques(lw.program, self._ops_f(lw).detach(), lw.ops_i, q.detach(), qd.detach(), T,
-                                                         self._n_dofs, plane, radius, springs, composed=bool(_composed))
+            ops_f = self._ops_f(lw).detach()
+        if differentiable and torch.is_grad_enabled() and (q.requires_grad or qd.requires_grad):
+            tau, force, moment = _ContactTorques.apply(q, qd, lw.program, ops_f, lw.ops_i, T, self._n_dofs, plane, radius, springs,
+                                                       bool(_composed))
+        else:
+            with torch.no_grad():
+                tau, force, moment = backend.contact_torques(lw.program, ops_f, lw.ops_i, q.detach(), qd.detach(), T, self._n_dofs, plane,
+                                                             radius, springs, composed=bool(_composed))
+        with torch.no_grad():
             force, moment = self._links_gather(force, sel, identity), self._links_gather(moment, sel, identity)
         return ContactTorques(*[x[0] if unbatched else x for x in (tau, force, moment)])
+
+    def compute_contact_torques_vjp(self, q: torch.Tensor, qd: torch.Tensor, grad_tau: torch.Tensor, contact: Optional[PlaneContact],
+                                    link_names: Optional[List[str]] = None, joint_limits: Optional[JointLimitSprings] = None, *,
+                                    _composed: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(grad_q, grad_qd) [B, n]: the vector-Jacobian product of compute_contact_torques' ``tau`` at q, qd under the cotangent
+        ``grad_tau`` [B, n], i.e. the gradients of grad_tau . tau with respect to q and qd — what the ``differentiable=True`` backward
+        launches, here for callers who want it without autograd.  ONE launch for all 8 links of a 7-DoF arm on full 64-row tiles
+        (csrc/drm_contact.hip: one sweep outwards that carries the link velocities at rates qd and at rates grad_tau together with the
+        law and its backward per link, one sweep inwards with three wrench sets); every other robot and link set composes the
+        link-motion launch twice, one element-wise kernel, the link-power-gradient launch twice, the external-torques launch and one
+        add.  No Jacobian and no kinematic Hessian is formed.  At a switch of the law the gradient is that of the branch
+        compute_contact_torques takes.  ``contact`` may be None when ``joint_limits`` is given (the springs' share alone).  Argument
+        handling and ``link_names``: compute_contact_torques'.  A row whose q, qd or grad_tau is not finite returns NaN and changes no
+        bit of any other row.  No autograd history."""
+        if contact is None and joint_limits is None:
+            raise ValueError("neither contact nor joint_limits")
+        unbatched, q, (qd, grad_tau) = self._links_args(q, [(qd, "qd"), (grad_tau, "grad_tau")], (self._n_dofs,))
+        assert qd is not None and grad_tau is not None, "qd and grad_tau must be given"
+        self._require_device()
+        with torch.no_grad():
+            lw, T, _, _, plane, radius, springs = self._contact_plan(contact, link_names, joint_limits)
+            if lw is None:          # (springs alone: any links walk, it is not walked)
+                lw, T, _, _ = self._links_plan(None)
+            gq, gqd = backend.contact_torques_vjp(lw.program, self._ops_f(lw).detach(), lw.ops_i, q.detach(), qd.detach(), grad_tau.detach(),
+                                                  T, self._n_dofs, plane, radius, springs, composed=bool(_composed))
+        return (gq[0], gqd[0]) if unbatched else (gq, gqd)
 
     def compute_contact_rollout(self, q0: torch.Tensor, qd0: torch.Tensor, tau: torch.Tensor, dt: float,
                                 contact: Optional[PlaneContact], link_names: Optional[List[str]] = None,
                                 joint_limits: Optional[JointLimitSprings] = None, integrator: str = "semi_implicit_euler",
                                 include_gravity: Optional[bool] = True, use_damping: Optional[bool] = False,
-                                return_acceleration: bool = False, *, _composed: bool = False) -> ContactRollout:
+                                return_acceleration: bool = False, *, differentiable: bool = False,
+                                _composed: bool = False) -> ContactRollout:
         """compute_forward_dynamics_rollout with contact: step t computes
             qdd_t = compute_forward_dynamics(q_t, qd_t, tau[t] + tau_ext(q_t, qd_t) + tau_lim(q_t, qd_t), include_gravity, use_damping)
         with tau_ext, tau_lim compute_contact_torques' at the state of the step, then the integrator's update.  Shapes, the
@@ -2425,9 +2467,15 @@ class DifferentiableRobotModel(torch.nn.Module):
         (the acceleration of each step) comes back with ``return_acceleration``.  ONE launch for a 7-DoF arm with all of its 8
         links in contact, on full 64-row tiles with B n a multiple of 4 (csrc/drm_contact.hip: the state stays in registers across
         the steps); every other case composes, per step, the contact torques, one add, the forward dynamics and the integrator on
-        the caller's stream.  ``contact=None`` needs ``joint_limits`` (the plain rollout exists for neither).  Forward only: a q0,
-        qd0 or tau that requires grad raises ValueError; the results carry no autograd history.  A row with a non-finite q0, qd0 or
-        tau gets non-finite results from that step on and changes no bit of any other row."""
+        the caller's stream.  ``contact=None`` needs ``joint_limits`` (the plain rollout exists for neither).  By default forward
+        only: a q0, qd0 or tau that requires grad raises ValueError; the results carry no autograd history.
+        ``differentiable=True`` opts in: the forward values are the same bits, and ``q`` and ``qd`` are DIFFERENTIABLE once with
+        respect to q0, qd0 and tau through ONE autograd node (autograd._ContactRollout) whose backward is a reverse sweep over the
+        steps — per step the two launches of compute_forward_dynamics' backward and one compute_contact_torques_vjp call, at the
+        states the forward returned.  At a switch of the law the gradient is that of the branch the forward took.  ``qdd`` comes
+        back detached; a second backward raises NotImplementedError; no gradient reaches learnable link parameters (their current
+        values are used) or the contact parameters: both walks' tables are constants of the node.  A row with a non-finite q0, qd0
+        or tau gets non-finite results from that step on and changes no bit of any other row."""
         if integrator not in self.ROLLOUT_INTEGRATORS:
             raise ValueError("integrator must be one of %s (got %r)" % (self.ROLLOUT_INTEGRATORS, integrator))
         if contact is None and joint_limits is None:
@@ -2445,7 +2493,8 @@ class DifferentiableRobotModel(torch.nn.Module):
             raise ValueError("a rollout takes at least one step (tau has T = 0)")
         if not (math.isfinite(dt) and dt > 0):
             raise ValueError("dt must be finite and positive (got %r)" % (dt,))
-        self._refuse_grad("compute_contact_rollout", q0=q0, qd0=qd0, tau=tau)
+        if not differentiable:
+            self._refuse_grad("compute_contact_rollout", q0=q0, qd0=qd0, tau=tau)
         single = q0.ndim == 1
         if single:
             q0, qd0, tau = q0.unsqueeze(0), qd0.unsqueeze(0), tau.unsqueeze(1)
@@ -2454,9 +2503,21 @@ class DifferentiableRobotModel(torch.nn.Module):
             dw = self._dynamics_walk()
             lw, T, _, _, plane, radius, springs = self._contact_plan(contact, link_names, joint_limits)
             links = (lw.program, self._ops_f(lw).detach(), lw.ops_i) if lw is not None else None
-            out = backend.contact_rollout((dw.program, self._ops_f(dw).detach(), dw.ops_i), links, q0.detach(), qd0.detach(), tau.detach(),
-                                          dt, bool(include_gravity), bool(use_damping), integrator == "euler", T, self._n_dofs, plane,
-                                          radius, springs, want_qdd=bool(return_acceleration), composed=bool(_composed))
+            dyn = (dw.program, self._ops_f(dw).detach(), dw.ops_i)
+        if differentiable and torch.is_grad_enabled() and (q0.requires_grad or qd0.requires_grad or tau.requires_grad):
+            vjp_links = links
+            if vjp_links is None:          # (springs alone: any links walk, the backward does not walk it)
+                with torch.no_grad():
+                    aw = self._links_plan(None)[0]
+                    vjp_links = (aw.program, self._ops_f(aw).detach(), aw.ops_i)
+            out = _ContactRollout.apply(q0, qd0, tau, dyn, links, vjp_links, dt, bool(include_gravity), bool(use_damping),
+                                        integrator == "euler", T, self._n_dofs, plane, radius, springs, bool(return_acceleration),
+                                        bool(_composed))
+        else:
+            with torch.no_grad():
+                out = backend.contact_rollout(dyn, links, q0.detach(), qd0.detach(), tau.detach(), dt, bool(include_gravity),
+                                              bool(use_damping), integrator == "euler", T, self._n_dofs, plane, radius, springs,
+                                              want_qdd=bool(return_acceleration), composed=bool(_composed))
         return ContactRollout(*[x[:, 0] if (single and x is not None) else x for x in out])
 
     def compute_inverse_dynamics_derivatives(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor,

@@ -784,6 +784,38 @@ int drm_contact_rollout(const drm_walk *dyn_walk, const drm_walk *links_walk, co
                         float *qd_traj, float *qdd_traj, float *scratch, void *stream);
 
 /*
+ * The vector-Jacobian product of drm_contact_torques in one call (additive to ABI 15): with tau_c(q, qd) that call's tau and grad_tau
+ * [B, n] a cotangent on it,
+ *   grad_q   [B, n]  d/dq  (grad_tau . tau_c)          grad_qd  [B, n]  d/dqd (grad_tau . tau_c)
+ * either may be NULL (not stored), not both; the other's bits do not depend on it.  No Jacobian and no kinematic Hessian is formed.
+ * With (a_t, b_t) = (lin_jac_t grad_tau, ang_jac_t grad_tau) the cotangents of the wrenches and (gp_t, gv_t, gw_t) the law's backward
+ * of them onto (p_t, v_t, w_t) (csrc/drm_contact.hpp contact_wrench_vjp):
+ *   grad_qd = drm_external_torques(q, gv, gw) - c_l grad_tau_j on an active spring
+ *   grad_q  = drm_link_power_dq(q, grad_tau, force, moment) + drm_external_torques(q, gp, 0) + drm_link_power_dq(q, qd, gv, gw)
+ *             - k_l grad_tau_j on an active spring
+ * The law is piecewise smooth: where depth, k depth - c v_n, c_t |v_t| - mu f_n, q - lower or upper - q changes sign the derivative is
+ * that of the branch drm_contact_torques takes at (q, qd); an exact tie of the two friction branches goes to the viscous one.
+ * links_walk, q, qd, n_targets, plane, radius, springs, lower, upper, flags (DRM_LINKS_COMPOSED), stream: drm_contact_torques', except
+ * that `plane` may be NULL when springs are given (the springs' share alone).  The same two forms: the 7-DoF arm chain of 8 ops, all
+ * targets in walk order, on full 64-row tiles with every pointer 16-byte aligned runs ONE launch, one row per lane — one sweep outwards
+ * that carries the velocities at rates qd and at rates grad_tau together with the law and its backward per link, one sweep inwards
+ * with the three wrench sets above, the two [64, 7] tiles out through LDS in 16-byte stores (84 B in, 56 B out per row).  Everything
+ * else, the B % 64 tail included, is composed on the caller's stream out of the one scratch: drm_link_motion twice (rates qd, rates
+ * grad_tau), one element-wise kernel for the law and its backward, drm_link_power_dq twice, drm_external_torques once, one add.
+ * A row whose q, qd or grad_tau is not finite (|q| beyond 1e5) gets NaN in both outputs and changes no bit of any other row.
+ *   scratch   drm_contact_torques_vjp_scratch_floats' floats (the _aligned form returns the same): the composed form over all B rows
+ * DRM_ERR_INVALID: a NULL q, qd or grad_tau, both outputs NULL, a plane or spring parameter that is not finite or is negative, a zero
+ * normal, B < 0, an n_targets outside [1, n_ops], neither plane nor springs; B == 0 returns DRM_OK.  Asynchronous on `stream`, no
+ * allocation, never a host synchronisation.
+ */
+int64_t drm_contact_torques_vjp_scratch_floats(const drm_walk *links_walk, int64_t B);
+int64_t drm_contact_torques_vjp_scratch_floats_aligned(const drm_walk *links_walk, int64_t B);
+int drm_contact_torques_vjp(const drm_walk *links_walk, const float *q, const float *qd, const float *grad_tau, int64_t B,
+                            int32_t n_targets, const drm_contact_plane *plane, const float *radius,
+                            const drm_joint_springs *springs, const float *lower, const float *upper, int32_t flags,
+                            float *grad_q, float *grad_qd, float *scratch, void *stream);
+
+/*
  * Collision: spheres fixed to the links against a world of spheres and oriented boxes shared by the whole batch, and against each
  * other through a list of sphere pairs (additive to ABI 15).  One call gives the cost and its q-gradient (drm_collision_cost) or the
  * sphere centres and their clearances (drm_sphere_distances).  The law (csrc/drm_collision.hpp), in float32 on explicit fused
