@@ -1439,8 +1439,9 @@ class DifferentiableRobotModel(torch.nn.Module):
                     if ent is not None:
                         self._fast_fkid[link_name] = ent
                 return out
-        plan = self.plan_fk_and_inverse_dynamics(q.detach(), qd.detach(), qdd_des.detach(), link_name,
-                                                 bool(include_gravity), bool(use_damping))
+        # (this plan lives for one launch: a row or column slice of a larger tensor is copied, as compute_inverse_dynamics does)
+        q, qd, qdd_des = (backend._dev_f32(t.detach(), name, self._n_dofs) for t, name in ((q, "q"), (qd, "qd"), (qdd_des, "qdd_des")))
+        plan = self.plan_fk_and_inverse_dynamics(q, qd, qdd_des, link_name, bool(include_gravity), bool(use_damping))
         with backend._on_device(self._device):
             plan.launch()
         return plan.tau, plan.pos, plan.quat

@@ -41,15 +41,42 @@ void jac_arm_8_7(const drm_walk *w, const float *q, int64_t B, float *pos, float
     }
 }
 
+// the arithmetic of rnea_arm_kernel<8, 7, LINKS>: LINKS = 8 (whole table) or 7 (tail folded: the sweeps stop at the last joint)
+template <int LINKS>
 void rnea_arm_8_7(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int flags, float *tau) {
-    constexpr int CAP = 8, NJ = 7;
+    constexpr int NJ = 7;
     for (int64_t b = 0; b < B; ++b) {
         float qv[NJ], qdv[NJ], qddv[NJ], tv[NJ];
         for (int d = 0; d < NJ; ++d) { qv[d] = q[b * NJ + d]; qdv[d] = qd[b * NJ + d]; qddv[d] = qdd ? qdd[b * NJ + d] : 0.f; }
-        Force park[CAP];
-        rnea_chain<CAP, NJ>([&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; }, flags & DRM_RNEA_GRAVITY,
-                            flags & DRM_RNEA_DAMPING, qv, qdv, qddv, tv, [&](int k, const Force &F) { park[k] = F; },
-                            [&](int k, Force &F) { F = park[k]; });
+        Force park[LINKS];
+        rnea_chain<LINKS, NJ>([&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; }, flags & DRM_RNEA_GRAVITY,
+                              flags & DRM_RNEA_DAMPING, qv, qdv, qddv, tv, [&](int k, const Force &F) { park[k] = F; },
+                              [&](int k, Force &F) { F = park[k]; });
+        for (int d = 0; d < NJ; ++d) tau[b * NJ + d] = tv[d];
+    }
+}
+
+// the arithmetic of fk_rnea_arm_kernel<8, 7, LINKS>: one sin / cos evaluation; the pose chain walks all 8 rows — rows 0 .. LINKS-1 of
+// the TREE walk's table, the fixed tail behind them from the CHAIN walk's — then the sweeps of rnea_arm_kernel on the first LINKS
+template <int LINKS>
+void fk_rnea_arm_8_7(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, const float *qdd, int64_t B, int flags,
+                     float *tau, float *pos, float *quat) {
+    constexpr int CAP = 8, NJ = 7;
+    auto row = [&](int k) { return (k < LINKS ? tree->ops_f : chain->ops_f) + k * DRM_OPF_STRIDE; };
+    for (int64_t b = 0; b < B; ++b) {
+        float qv[NJ], qdv[NJ], qddv[NJ], tv[NJ], cs[NJ], sn[NJ];
+        for (int d = 0; d < NJ; ++d) { qv[d] = q[b * NJ + d]; qdv[d] = qd[b * NJ + d]; qddv[d] = qdd ? qdd[b * NJ + d] : 0.f; }
+        chain_trig<NJ>(qv, cs, sn);
+        PoseP ee;
+        f2 Bk[NJ][3];
+        fk_chain_pairs_trig<CAP, NJ>(row, cs, sn, ee, Bk, [] {});
+        for (int i = 0; i < 3; ++i) pos[b * 3 + i] = ee.B[i][1];
+        Pose E;
+        pose_from_pairs(ee, E);
+        quat_xyzw(E.R, quat + b * 4);
+        Force park[LINKS];
+        rnea_chain_trig<LINKS, NJ>(row, flags & DRM_RNEA_GRAVITY, flags & DRM_RNEA_DAMPING, cs, sn, qdv, qddv, tv,
+                                   [&](int k, const Force &F) { park[k] = F; }, [&](int k, Force &F) { F = park[k]; });
         for (int d = 0; d < NJ; ++d) tau[b * NJ + d] = tv[d];
     }
 }
@@ -245,7 +272,19 @@ int emu_fk_jacobian_arm(const drm_walk *w, const float *q, int64_t B, float *pos
 }
 int emu_rnea_arm(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau) {
     if (!(w->shape & DRM_WALK_ARM_CHAIN) || w->capacity != 8 || w->n_dofs != 7) return -2;
-    rnea_arm_8_7(w, q, qd, qdd, B, flags, tau);
+    if (w->n_ops == 7) rnea_arm_8_7<7>(w, q, qd, qdd, B, flags, tau);
+    else rnea_arm_8_7<8>(w, q, qd, qdd, B, flags, tau);
+    return 0;
+}
+// drm_fk_rnea's fused arm rung (fk_rnea_arm_applies): the tree walk IS the chain (8 ops on both), or the tree walk holds the 7 moving
+// joints and the chain walk the fixed tail behind them
+int emu_fk_rnea_arm(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags,
+                    float *tau, float *pos, float *quat) {
+    if (!(tree->shape & DRM_WALK_ARM_CHAIN) || tree->capacity != 8 || tree->n_dofs != 7) return -2;
+    if (!(chain->shape & DRM_WALK_ARM_CHAIN) || chain->capacity != 8 || chain->n_ops != 8 || chain->target_perm != 2) return -2;
+    if (tree->n_ops == 7) fk_rnea_arm_8_7<7>(tree, chain, q, qd, qdd, B, flags, tau, pos, quat);
+    else if (tree->n_ops == 8) fk_rnea_arm_8_7<8>(tree, chain, q, qd, qdd, B, flags, tau, pos, quat);
+    else return -2;
     return 0;
 }
 int emu_rnea_arm_hand(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau) {
