@@ -63,18 +63,30 @@ __device__ __forceinline__ void chain_trig_all(const float (&q)[CAP], float (&cs
     bool big = false;
 #pragma unroll
     for (int k = 0; k < TRIG; ++k) big = big || !(fabsf(q[k]) <= SINCOS_PAIR_MAX_ARG);
-    if (DRM_WAVE_ANY(big)) { // rare; wave-uniform
+    auto packed = [&](const float (&a)[CAP]) {
 #pragma unroll
-        for (int k = 0; k < TRIG; ++k) sincos_f(q[k], sn[k], cs[k]);
+        for (int k = 0; k < TRIG; k += 2) {
+            f2 s2, c2;
+            sincos_pair(f2_make(a[k], a[k + 1 < TRIG ? k + 1 : k]), s2, c2);
+            sn[k] = s2[0]; cs[k] = c2[0];
+            if (k + 1 < TRIG) { sn[k + 1] = s2[1]; cs[k + 1] = c2[1]; }
+        }
+    };
+    // rare; entered by the whole wavefront, but only the lanes that hold a large or non-finite angle take sincos_f's values: the others
+    // keep the packed evaluation's, bit for bit (drm_sample.hpp chain_trig), so that a row never depends on the rows of its wavefront
+    if (DRM_WAVE_ANY_RARE(big)) {
+        float qr[CAP];
+#pragma unroll
+        for (int k = 0; k < CAP; ++k) qr[k] = k < TRIG ? DRM_RARE_COPY(q[k]) : 0.0f;
+        if (big) {
+#pragma unroll
+            for (int k = 0; k < TRIG; ++k) sincos_f(qr[k], sn[k], cs[k]);
+        } else {
+            packed(qr);
+        }
         return;
     }
-#pragma unroll
-    for (int k = 0; k < TRIG; k += 2) {
-        f2 s2, c2;
-        sincos_pair(f2_make(q[k], q[k + 1 < TRIG ? k + 1 : k]), s2, c2);
-        sn[k] = s2[0]; cs[k] = c2[0];
-        if (k + 1 < TRIG) { sn[k + 1] = s2[1]; cs[k + 1] = c2[1]; }
-    }
+    packed(q);
 }
 
 // this lane's joint angles, one dword load per op at a wave-uniform column (ops that do not move: column 0, value dropped).

@@ -764,6 +764,22 @@ def test_all_links_fk_beyond_the_infinity_cache():
         assert max_err(host(p[rows]), op[:, i]) <= TOL_POS["atol"], name
         ok, _ = quat_close(host(r[rows]), oq[:, i], TOL_QUAT["atol"])
         assert ok, name
+    # ... and every link at its own scale: the metrics, yardstick and requirement of tests/test_fk_rungs.py on the same rows
+    from test_fk_rungs import FLOOR, MARGIN, line, quat_error
+    yp, yq = Oracle(m._spec).fk(q[rows], list(range(len(names))), np.float32)
+    failures = []
+    for i, name in enumerate(names):
+        p, r = host(poses[name][0][rows]), host(poses[name][1][rows])
+        reach = float(np.abs(op[:, i]).max())
+        if reach == 0:
+            assert not p.any(), name
+            continue
+        for metric, e, y in (("pos", max_err(p, op[:, i]) / reach, max_err(yp[:, i], op[:, i]) / reach),
+                             ("quat", quat_error(r, oq[:, i]), quat_error(yq[:, i], oq[:, i]))):
+            line("iiwa7_allegro", name, "all-links-past-llc", 61, metric, e, max(y, FLOOR))
+            if not e <= MARGIN * max(y, FLOOR):
+                failures.append((name, metric, e, y))
+    assert not failures, failures
 
 
 @pytest.mark.gpu
