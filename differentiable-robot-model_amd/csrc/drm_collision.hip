@@ -52,6 +52,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_links.hpp"
 #include "drm_rows.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -474,34 +475,8 @@ static CollScratch coll_scratch_plan(const drm_walk *w, int64_t rows, int T, int
     return p;
 }
 
-// what both entry points ask of their arguments
-static int coll_check(const drm_walk *w, const float *q, int64_t B, int T, const drm_collision_spheres *spheres, const drm_collision_world *world,
-                      const drm_collision_pairs *pairs, CollArgs &a) {
-    a = CollArgs{};
-    int rc = rows_check_walk(w);
-    if (rc) return rc;
-    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-    if (!spheres || !spheres->spheres || !spheres->start) return fail(DRM_ERR_INVALID, "spheres, their table and their offsets must not be NULL");
-    if (spheres->n_spheres < 1) return fail(DRM_ERR_INVALID, "at least one sphere");
-    a.sph = spheres->spheres;
-    a.start = spheres->start;
-    a.S = spheres->n_spheres;
-    if (world) {
-        if (world->n_spheres < 0 || world->n_boxes < 0) return fail(DRM_ERR_INVALID, "negative obstacle count");
-        if ((world->n_spheres > 0 && !world->spheres) || (world->n_boxes > 0 && !world->boxes))
-            return fail(DRM_ERR_INVALID, "a world table is NULL");
-        a.ws = world->spheres; a.n_ws = world->n_spheres;
-        a.wb = world->boxes; a.n_wb = world->n_boxes;
-    }
-    if (pairs) {
-        if (pairs->n_pairs < 0) return fail(DRM_ERR_INVALID, "negative pair count");
-        if (pairs->n_pairs > 0 && !pairs->pairs) return fail(DRM_ERR_INVALID, "the pair list is NULL");
-        a.pairs = pairs->pairs; a.P = pairs->n_pairs;
-    }
-    return DRM_OK;
-}
+// the checked tables of a call (drm_args.hpp args_collision) as the kernels take them
+static CollArgs coll_args(const CollTables &t) { return CollArgs{t.spheres, t.start, t.S, t.ws, t.wb, t.n_ws, t.n_wb, t.pairs, t.P, t.world, t.self}; }
 
 // an arm7_walk of 8 ops whose every op is a target, slots in walk order (drm_links.hip links_fused), and tables within the caps
 static inline bool coll_fused(const drm_walk *w, int T, int64_t B, int flags, bool aligned, const CollArgs &a) {
@@ -540,13 +515,13 @@ using namespace drm;
 
 // The general path over ALL B rows, whatever the alignment, the targets and the caps (drm_links.hip links_scratch).
 static int64_t coll_query(const drm_walk *w, int64_t B, int32_t S) {
-    if (rows_check_walk(w) || B <= 0 || S < 1) return 0;
+    if (check_sweep_walk(w) || B <= 0 || S < 1) return 0;
     return coll_scratch_plan(w, B, w->n_ops, S).total;
 }
 // The same for a call without DRM_LINKS_COMPOSED whose pointers are all 16-byte aligned, of which the query is told what else
 // decides whether the fused kernel takes the full tiles (coll_fused): then only the tail of B % 64 rows is left to the general path.
 static int64_t coll_query_aligned(const drm_walk *w, int64_t B, int32_t T, int32_t S, int32_t n_obstacles, int32_t n_pairs) {
-    if (rows_check_walk(w) || B <= 0 || S < 1) return 0;
+    if (check_sweep_walk(w) || B <= 0 || S < 1) return 0;
     if (T < 1 || T > w->n_ops || n_obstacles < 0 || n_pairs < 0) return coll_query(w, B, S);
     CollArgs a{};
     a.S = S;
@@ -570,19 +545,11 @@ extern "C" int64_t drm_sphere_distances_scratch_floats_aligned(const drm_walk *w
 extern "C" int drm_collision_cost(const drm_walk *w, const float *q, int64_t B, int32_t n_targets, const drm_collision_spheres *spheres,
                                   const drm_collision_world *world, const drm_collision_pairs *pairs, const drm_collision_params *params,
                                   int32_t flags, float *cost, float *dq, float *scratch, void *stream) {
-    CollArgs a;
-    int rc = coll_check(w, q, B, n_targets, spheres, world, pairs, a);
+    CollTables tables;
+    int rc = args_collision_cost(w, q, B, n_targets, spheres, world, pairs, params, cost, dq, tables);
     if (rc) return rc;
-    if (!world && !pairs) return fail(DRM_ERR_INVALID, "neither a world nor pairs");
-    if (!params) return fail(DRM_ERR_INVALID, "params must not be NULL");
-    if (!cost && !dq) return fail(DRM_ERR_INVALID, "cost and dq are both NULL");
-    if (world && !coll_law_ok(params->world_weight, params->world_activation))
-        return fail(DRM_ERR_INVALID, "the world weight must be finite and >= 0, its activation distance finite and > 0");
-    if (pairs && !coll_law_ok(params->self_weight, params->self_activation))
-        return fail(DRM_ERR_INVALID, "the self weight must be finite and >= 0, its activation distance finite and > 0");
-    a.world = world ? coll_law_make(params->world_weight, params->world_activation) : coll_law_make(0.0f, 1.0f);
-    a.self = pairs ? coll_law_make(params->self_weight, params->self_activation) : coll_law_make(0.0f, 1.0f);
     if (B == 0) return DRM_OK;
+    const CollArgs a = coll_args(tables);
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs, T = n_targets;
     int64_t lo = 0;
@@ -612,12 +579,11 @@ extern "C" int drm_collision_cost(const drm_walk *w, const float *q, int64_t B, 
 extern "C" int drm_sphere_distances(const drm_walk *w, const float *q, int64_t B, int32_t n_targets, const drm_collision_spheres *spheres,
                                     const drm_collision_world *world, const drm_collision_pairs *pairs, int32_t flags, float *center,
                                     float *world_distance, float *self_distance, float *scratch, void *stream) {
-    CollArgs a;
-    int rc = coll_check(w, q, B, n_targets, spheres, world, pairs, a);
+    CollTables tables;
+    int rc = args_sphere_distances(w, q, B, n_targets, spheres, world, pairs, center, world_distance, self_distance, tables);
     if (rc) return rc;
-    if (!center && !world_distance && !self_distance) return fail(DRM_ERR_INVALID, "every output is NULL");
-    a.world = a.self = coll_law_make(0.0f, 1.0f);
     if (B == 0) return DRM_OK;
+    const CollArgs a = coll_args(tables);
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs, T = n_targets, S = a.S;
     int64_t lo = 0;

@@ -51,6 +51,7 @@
 #include "drm_rollout.hpp"
 #include "drm_rows.hpp"
 #include "drm_sample.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -413,35 +414,15 @@ static inline bool contact_links_fused(const drm_walk *w, int T, int64_t B, int 
     return !(flags & DRM_LINKS_COMPOSED) && (w->shape & DRM_WALK_TARGETS_ORDERED) && w->n_ops == 8 && T == 8 && rows_fused(w, B, aligned);
 }
 
+// the checked contact arguments (drm_args.hpp ContactPlan) as the kernels take them
 struct ContactArgs {
     ContactPlane pl;
     int has_plane;
     const float *radius;
     SpringArgs sp;
 };
-
-// what both entry points ask of their contact arguments
-static int contact_check(const drm_walk *lw, int64_t B, int T, const drm_contact_plane *plane, const float *radius,
-                         const drm_joint_springs *springs, const float *lower, const float *upper, ContactArgs &a) {
-    a = ContactArgs{};
-    if (!plane && !springs) return fail(DRM_ERR_INVALID, "neither a contact plane nor joint-limit springs");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (plane) {
-        int rc = rows_check_walk(lw);
-        if (rc) return rc;
-        if (T < 1 || T > lw->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-        const int bad = contact_plane_make(plane, a.pl);
-        if (bad == 1) return fail(DRM_ERR_INVALID, "the plane's offset must be finite, its stiffness, damping, friction and slope finite and >= 0");
-        if (bad) return fail(DRM_ERR_INVALID, "the plane's normal must be finite and not zero");
-        a.has_plane = 1;
-        a.radius = radius;
-    }
-    if (springs) {
-        if (!joint_springs_ok(springs)) return fail(DRM_ERR_INVALID, "the joint springs' stiffness and damping must be finite and >= 0");
-        if (!lower || !upper) return fail(DRM_ERR_INVALID, "joint springs need lower and upper");
-        a.sp = SpringArgs{springs->stiffness, springs->damping, lower, upper, 1};
-    }
-    return DRM_OK;
+static ContactArgs contact_args(const ContactPlan &p) {
+    return ContactArgs{p.pl, p.has_plane, p.radius, SpringArgs{p.k, p.c, p.lower, p.upper, p.lower != nullptr}};
 }
 
 // The composed contact torques of `rows` rows: out = tau_in + (tau_ext + tau_lim).  `buf`: 5 x r4(rows T 3) + r4(rows n) floats (the
@@ -483,7 +464,7 @@ using namespace drm;
 // The composed form over ALL B rows, whatever the alignment: whether a call is fused depends on n_targets, which the query does not
 // see (drm_links.hip links_scratch).
 extern "C" int64_t drm_contact_torques_scratch_floats(const drm_walk *lw, int64_t B) {
-    if (rows_check_walk(lw) || B <= 0) return 0;
+    if (check_sweep_walk(lw) || B <= 0) return 0;
     return contact_buf_floats(B, lw->n_ops, lw->n_dofs) + contact_links_sub(lw, B);
 }
 extern "C" int64_t drm_contact_torques_scratch_floats_aligned(const drm_walk *lw, int64_t B) { return drm_contact_torques_scratch_floats(lw, B); }
@@ -492,14 +473,11 @@ extern "C" int drm_contact_torques(const drm_walk *lw, const float *q, const flo
                                    const drm_contact_plane *plane, const float *radius, const drm_joint_springs *springs,
                                    const float *lower, const float *upper, int32_t flags, float *tau, float *force, float *moment,
                                    float *scratch, void *stream) {
-    int rc = rows_check_walk(lw);
-    if (rc) return rc;
-    if (!q || !qd || !tau) return fail(DRM_ERR_INVALID, "q / qd / tau must not be NULL");
-    if (!plane) return fail(DRM_ERR_INVALID, "drm_contact_torques needs a plane");
-    ContactArgs a;
-    rc = contact_check(lw, B, n_targets, plane, radius, springs, lower, upper, a);
+    ContactPlan plan;
+    int rc = args_contact_torques(lw, q, qd, B, n_targets, plane, radius, springs, lower, upper, tau, plan);
     if (rc) return rc;
     if (B == 0) return DRM_OK;
+    const ContactArgs a = contact_args(plan);
     hipStream_t s = (hipStream_t)stream;
     const int n = lw->n_dofs, T = n_targets;
     int64_t lo = 0;
@@ -558,7 +536,7 @@ static int contact_vjp_composed(const drm_walk *lw, const ContactArgs &a, const 
 
 // The composed form over ALL B rows, as drm_contact_torques_scratch_floats.
 extern "C" int64_t drm_contact_torques_vjp_scratch_floats(const drm_walk *lw, int64_t B) {
-    if (rows_check_walk(lw) || B <= 0) return 0;
+    if (check_sweep_walk(lw) || B <= 0) return 0;
     return contact_vjp_buf_floats(B, lw->n_ops, lw->n_dofs) + contact_vjp_links_sub(lw, B);
 }
 extern "C" int64_t drm_contact_torques_vjp_scratch_floats_aligned(const drm_walk *lw, int64_t B) {
@@ -569,14 +547,11 @@ extern "C" int drm_contact_torques_vjp(const drm_walk *lw, const float *q, const
                                        int32_t n_targets, const drm_contact_plane *plane, const float *radius,
                                        const drm_joint_springs *springs, const float *lower, const float *upper, int32_t flags,
                                        float *grad_q, float *grad_qd, float *scratch, void *stream) {
-    int rc = rows_check_walk(lw);
-    if (rc) return rc;
-    if (!q || !qd || !grad_tau) return fail(DRM_ERR_INVALID, "q / qd / grad_tau must not be NULL");
-    if (!grad_q && !grad_qd) return fail(DRM_ERR_INVALID, "grad_q and grad_qd are both NULL");
-    ContactArgs a;
-    rc = contact_check(lw, B, n_targets, plane, radius, springs, lower, upper, a);
+    ContactPlan plan;
+    int rc = args_contact_torques_vjp(lw, q, qd, grad_tau, B, n_targets, plane, radius, springs, lower, upper, grad_q, grad_qd, plan);
     if (rc) return rc;
     if (B == 0) return DRM_OK;
+    const ContactArgs a = contact_args(plan);
     hipStream_t s = (hipStream_t)stream;
     const int n = lw->n_dofs, T = n_targets;
     int64_t lo = 0;
@@ -608,7 +583,7 @@ static int64_t contact_rollout_scratch_impl(const drm_walk *dw, const drm_walk *
     const int n = dw->n_dofs;
     const int64_t fd = aligned && (B * n) % 4 == 0 ? drm_forward_dynamics_scratch_floats_aligned(dw, B) : drm_forward_dynamics_scratch_floats(dw, B);
     int64_t links = 0, buf = 0;
-    if (lw && !rows_check_walk(lw)) {
+    if (lw && !check_sweep_walk(lw)) {
         links = contact_links_sub(lw, B);
         buf = contact_buf_floats(B, lw->n_ops, n);
     }
@@ -625,16 +600,11 @@ extern "C" int drm_contact_rollout(const drm_walk *dw, const drm_walk *lw, const
                                    int32_t T, float dt, int32_t flags, int32_t n_targets, const drm_contact_plane *plane,
                                    const float *radius, const drm_joint_springs *springs, const float *lower, const float *upper,
                                    float *q_traj, float *qd_traj, float *qdd_traj, float *scratch, void *stream) {
-    int rc = check_walk(dw);
+    ContactPlan plan;
+    int rc = args_contact_rollout(dw, lw, q0, qd0, tau, B, T, dt, n_targets, plane, radius, springs, lower, upper, q_traj, qd_traj, plan);
     if (rc) return rc;
-    if (!q0 || !qd0 || !tau || !q_traj || !qd_traj) return fail(DRM_ERR_INVALID, "q0 / qd0 / tau / q_traj / qd_traj must not be NULL");
-    if (T < 1) return fail(DRM_ERR_INVALID, "a rollout takes at least one step (T = %s%ld)", "", (long)T);
-    if (!(dt > 0.0f) || !isfinite(dt)) return fail(DRM_ERR_INVALID, "dt must be finite and positive");
-    ContactArgs a;
-    rc = contact_check(lw, B, n_targets, plane, radius, springs, lower, upper, a);
-    if (rc) return rc;
-    if (plane && lw->n_dofs != dw->n_dofs) return fail(DRM_ERR_INVALID, "the two walks are not of one robot");
     if (B == 0) return DRM_OK;
+    const ContactArgs a = contact_args(plan);
     hipStream_t s = (hipStream_t)stream;
     const int n = dw->n_dofs, TL = n_targets;
     const bool aligned = aligned16(q0, qd0, tau, q_traj, qd_traj, qdd_traj) && (!plane || table_aligned(lw));

@@ -36,44 +36,19 @@
 #include "drm_rollout.hpp"
 #include "drm_rows.hpp"
 
+// the error of the calling thread's last refused call, in the signature the .hip units' drm_common.hpp declares (drm_args.hpp)
+namespace drm {
+int fail(int code, const char *fmt, const char *a = "", long b = 0, long c = 0);
+}
+#include "drm_args.hpp"
+
 namespace {
 using namespace drm_host;
+using drm::fail;
 
 constexpr int64_t CHUNK = 256; // rows per work item (and per partial sum of the backward calls)
 thread_local char g_err[512] = "";
 std::atomic<int> g_threads{0}; // 0: hardware_concurrency (or DRM_CPU_THREADS)
-
-int fail(int code, const char *fmt, long a = 0, long b = 0) {
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return code;
-}
-
-int check_walk(const drm_walk *w) {
-    if (!w) return fail(DRM_ERR_INVALID, "walk is NULL");
-    if (!w->ops_f || !w->ops_i) return fail(DRM_ERR_INVALID, "walk tables are NULL");
-    const int c = w->capacity;
-    if (c < 4 || (c & 3) || c > 0xffff) return fail(DRM_ERR_INVALID, "walk capacity %ld is not a multiple of 4 in [4, 65535]", c);
-    if (w->n_ops < 0 || w->n_ops > c) return fail(DRM_ERR_INVALID, "walk has %ld ops but capacity %ld", w->n_ops, c);
-    if (w->n_dofs < 1 || w->n_dofs > DRM_MAX_DOFS) return fail(DRM_ERR_UNSUPPORTED, "n_dofs %ld outside [1, %ld]", w->n_dofs, DRM_MAX_DOFS);
-    if (w->n_slots < 0 || w->n_slots > DRM_MAX_SLOTS)
-        return fail(DRM_ERR_UNSUPPORTED, "walk needs %ld save slots, the walks have %ld", w->n_slots, DRM_MAX_SLOTS);
-    if (w->n_segments < 1 || w->n_segments > DRM_MAX_SEGMENTS) return fail(DRM_ERR_INVALID, "walk has %ld segments", w->n_segments);
-    return DRM_OK;
-}
-
-// what the tree-sweep entry points (regressor, H / C / g, inverse-dynamics derivatives, energies) ask of a walk
-int check_sweep_walk(const drm_walk *w) {
-    if (int rc = check_walk(w)) return rc;
-    return w->n_ops < 1 ? fail(DRM_ERR_INVALID, "the walk has no ops") : DRM_OK;
-}
-
-int check_backward_walk(const drm_walk *w, uint64_t mask) {
-    if (int rc = check_walk(w)) return rc;
-    if (w->capacity > DRM_MAX_OPS) return fail(DRM_ERR_UNSUPPORTED, "backward walks take at most %ld ops (capacity %ld)", DRM_MAX_OPS, w->capacity);
-    if (w->n_slots > DRM_MAX_SLOTS_BACKWARD) return fail(DRM_ERR_UNSUPPORTED, "backward walks take at most %ld save slots (%ld)", DRM_MAX_SLOTS_BACKWARD, w->n_slots);
-    if (w->capacity < 64 && (mask >> w->capacity)) return fail(DRM_ERR_INVALID, "param_mask selects ops beyond the walk's capacity");
-    return DRM_OK;
-}
 
 int64_t n_chunks(int64_t B) { return (B + CHUNK - 1) / CHUNK; }
 
@@ -120,9 +95,7 @@ void reduce_partials(const float *partials, int64_t chunks, int entries, float *
 }
 
 int fk_any(const drm_walk *w, const float *q, int64_t B, int T, float *pos, float *quat, bool link_major) {
-    if (int rc = check_walk(w)) return rc;
-    if (B < 0 || T < 1) return fail(DRM_ERR_INVALID, "bad batch (%ld) or target count (%ld)", (long)B, T);
-    if (!q || !pos || !quat) return fail(DRM_ERR_INVALID, "q / pos / quat must not be NULL");
+    if (int rc = drm::args_fk(w, q, B, T, pos, quat)) return rc;
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         if (link_major)
@@ -134,10 +107,7 @@ int fk_any(const drm_walk *w, const float *q, int64_t B, int T, float *pos, floa
 }
 
 int fk_fan(const drm_walk *chains, int T, const float *q, int64_t B, float *pos, float *quat, bool link_major) {
-    if (!chains || T < 2 || T > 4) return fail(DRM_ERR_INVALID, "drm_fk_fanout takes 2 .. 4 chains (%ld)", T);
-    for (int t = 0; t < T; ++t)
-        if (int rc = check_walk(chains + t)) return rc;
-    if (B < 0 || !q || !pos || !quat) return fail(DRM_ERR_INVALID, "bad batch or NULL q / pos / quat");
+    if (int rc = drm::args_fk_fanout(chains, T, q, B, pos, quat)) return rc;
     const int n = chains[0].n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         for (int t = 0; t < T; ++t) {
@@ -147,12 +117,6 @@ int fk_fan(const drm_walk *chains, int T, const float *q, int64_t B, float *pos,
                 fk_loop(chains + t, q + b0 * n, rows, 1, pos + (b0 * T + t) * 3, quat + (b0 * T + t) * 4, T, 0);
         }
     });
-    return DRM_OK;
-}
-
-int rnea_checked(const drm_walk *w, const float *q, const float *qd, const float *tau, int64_t B) {
-    if (int rc = check_walk(w)) return rc;
-    if (B < 0 || !q || !qd || !tau) return fail(DRM_ERR_INVALID, "bad batch or NULL q / qd / output");
     return DRM_OK;
 }
 
@@ -474,39 +438,11 @@ void link_power_dq_host_rows(const drm_walk *w, const float *q, const float *qd,
             [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); }, wrench, jout);
     }
 }
-// what drm_contact_torques and drm_contact_rollout ask of their contact arguments (drm_contact.hip contact_check)
-struct ContactArgs {
-    drm::ContactPlane pl;
-    bool has_plane;
-    const float *radius;
-    float k, c;
-    const float *lower, *upper; // NULL: no joint-limit springs
-};
-int contact_check(const drm_walk *lw, int64_t B, int T, const drm_contact_plane *plane, const float *radius, const drm_joint_springs *springs,
-                  const float *lower, const float *upper, ContactArgs &a) {
-    a = ContactArgs{};
-    if (!plane && !springs) return fail(DRM_ERR_INVALID, "neither a contact plane nor joint-limit springs");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (plane) {
-        if (int rc = check_sweep_walk(lw)) return rc;
-        if (T < 1 || T > lw->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-        const int bad = drm::contact_plane_make(plane, a.pl);
-        if (bad == 1) return fail(DRM_ERR_INVALID, "the plane's offset must be finite, its stiffness, damping, friction and slope finite and >= 0");
-        if (bad) return fail(DRM_ERR_INVALID, "the plane's normal must be finite and not zero");
-        a.has_plane = true;
-        a.radius = radius;
-    }
-    if (springs) {
-        if (!drm::joint_springs_ok(springs)) return fail(DRM_ERR_INVALID, "the joint springs' stiffness and damping must be finite and >= 0");
-        if (!lower || !upper) return fail(DRM_ERR_INVALID, "joint springs need lower and upper");
-        a.k = springs->stiffness; a.c = springs->damping; a.lower = lower; a.upper = upper;
-    }
-    return DRM_OK;
-}
+using drm::ContactPlan;
 // out = tau_in + (tau_ext + tau_lim) of `rows` rows from q, qd on (all pointers at the first of them; tau_in, force, moment may be
 // NULL): the chain form where drm_contact.hip would launch its fused kernels, elsewhere its composition of the link sweeps and the law.
 // check_rows: a row whose q or qd cannot be used gets NaN (drm_contact_torques).
-void contact_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q, const float *qd, const float *tau_in, int64_t rows, int T,
+void contact_host_rows(const drm_walk *lw, const ContactPlan &a, const float *q, const float *qd, const float *tau_in, int64_t rows, int T,
                        int n, int flags, bool check_rows, float *out, float *force, float *moment) {
     const float nan = std::numeric_limits<float>::quiet_NaN();
     std::vector<float> ext((size_t)rows * n, 0.0f);
@@ -556,7 +492,7 @@ void contact_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q,
 }
 // drm_contact_torques_vjp of `rows` rows from q, qd, lam on (grad_q or grad_qd may be NULL): the chain form where drm_contact.hip would
 // launch its fused kernel, elsewhere its composition of the link sweeps, the law's backward and the q-gradients of the sweeps.
-void contact_vjp_host_rows(const drm_walk *lw, const ContactArgs &a, const float *q, const float *qd, const float *lam, int64_t rows, int T,
+void contact_vjp_host_rows(const drm_walk *lw, const ContactPlan &a, const float *q, const float *qd, const float *lam, int64_t rows, int T,
                            int n, int flags, float *grad_q, float *grad_qd) {
     const float nan = std::numeric_limits<float>::quiet_NaN();
     const size_t N = (size_t)rows * n;
@@ -602,31 +538,6 @@ void contact_vjp_host_rows(const drm_walk *lw, const ContactArgs &a, const float
             if (grad_qd) grad_qd[i] = bad ? nan : y;
         }
     }
-}
-// what drm_collision_cost and drm_sphere_distances ask of their arguments (drm_collision.hip coll_check)
-int collision_check(const drm_walk *w, const float *q, int64_t B, int T, const drm_collision_spheres *spheres, const drm_collision_world *world,
-                    const drm_collision_pairs *pairs, drm::CollTables &t) {
-    t = drm::CollTables{};
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-    if (!spheres || !spheres->spheres || !spheres->start) return fail(DRM_ERR_INVALID, "spheres, their table and their offsets must not be NULL");
-    if (spheres->n_spheres < 1) return fail(DRM_ERR_INVALID, "at least one sphere");
-    t.spheres = spheres->spheres; t.start = spheres->start; t.S = spheres->n_spheres; t.T = T;
-    if (world) {
-        if (world->n_spheres < 0 || world->n_boxes < 0) return fail(DRM_ERR_INVALID, "negative obstacle count");
-        if ((world->n_spheres > 0 && !world->spheres) || (world->n_boxes > 0 && !world->boxes))
-            return fail(DRM_ERR_INVALID, "a world table is NULL");
-        t.ws = world->spheres; t.n_ws = world->n_spheres; t.wb = world->boxes; t.n_wb = world->n_boxes;
-    }
-    if (pairs) {
-        if (pairs->n_pairs < 0) return fail(DRM_ERR_INVALID, "negative pair count");
-        if (pairs->n_pairs > 0 && !pairs->pairs) return fail(DRM_ERR_INVALID, "the pair list is NULL");
-        t.pairs = pairs->pairs; t.P = pairs->n_pairs;
-    }
-    t.world = t.self = drm::coll_law_make(0.0f, 1.0f);
-    return DRM_OK;
 }
 // drm_collision_cost (cost, dq) / drm_sphere_distances (center, wd, sd) of `rows` rows (all pointers at the first of them, any may be
 // NULL): the targets' frames by the chain form where drm_collision.hip would launch its fused kernel, by the general walk elsewhere;
@@ -677,6 +588,11 @@ void collision_host_rows(const drm_walk *w, const drm::CollTables &t, const floa
 }
 } // namespace
 
+int drm::fail(int code, const char *fmt, const char *a, long b, long c) {
+    snprintf(g_err, sizeof(g_err), fmt, a, b, c);
+    return code;
+}
+
 extern "C" {
 int drm_abi_version(void) { return DRM_ABI_VERSION; }
 int drm_walk_sizeof(void) { return (int)sizeof(drm_walk); }
@@ -701,8 +617,7 @@ int drm_fk_fanout_links(const drm_walk *chains, int32_t T, const float *q, int64
 }
 
 int drm_fk_jacobian(const drm_walk *w, const float *q, int64_t B, float *pos, float *quat, float *lin, float *ang, void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (B < 0 || !q || !lin || !ang) return fail(DRM_ERR_INVALID, "bad batch or NULL q / lin_jac / ang_jac");
+    if (int rc = drm::args_fk_jacobian(w, q, B, lin, ang)) return rc;
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         jac_loop(w, q + b0 * n, rows, pos ? pos + b0 * 3 : nullptr, quat ? quat + b0 * 4 : nullptr, lin + b0 * 3 * n, ang + b0 * 3 * n);
@@ -720,7 +635,7 @@ int64_t drm_forward_dynamics_scratch_floats_aligned(const drm_walk *, int64_t) {
 
 int drm_rnea(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau, float *,
              void *) {
-    if (int rc = rnea_checked(w, q, qd, tau, B)) return rc;
+    if (int rc = drm::args_rnea(w, q, qd, B, tau)) return rc;
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         rnea_loop(w, q + b0 * n, qd + b0 * n, qdd ? qdd + b0 * n : nullptr, rows, flags, tau + b0 * n);
@@ -730,9 +645,7 @@ int drm_rnea(const drm_walk *w, const float *q, const float *qd, const float *qd
 
 int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t, const float *q, const float *qd, const float *qdd, int64_t B,
                 int32_t flags, float *tau, float *pos, float *quat, float *, void *) {
-    if (int rc = rnea_checked(tree, q, qd, tau, B)) return rc;
-    if (int rc = check_walk(chain)) return rc;
-    if (!pos || !quat) return fail(DRM_ERR_INVALID, "pos / quat must not be NULL");
+    if (int rc = drm::args_fk_rnea(tree, chain, q, qd, B, tau, pos, quat)) return rc;
     const int n = tree->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         rnea_loop(tree, q + b0 * n, qd + b0 * n, qdd ? qdd + b0 * n : nullptr, rows, flags, tau + b0 * n);
@@ -744,8 +657,7 @@ int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t, const floa
 // ABI 11: the host build of the one-sided gather — the destinations are host arrays (e.g. shared-memory tensors of the other ranks)
 int drm_fk_rnea_put(const drm_walk *tree, const drm_walk *chain, int32_t target_op, const float *q, const float *qd, const float *qdd,
                     int64_t B, int32_t flags, float *tau, float *pos, float *quat, float *scratch, const drm_put *put, void *stream) {
-    if (put && (put->n_peers < 0 || put->n_peers > DRM_MAX_PEERS || put->row_offset < 0))
-        return fail(DRM_ERR_INVALID, "drm_put: n_peers must be 0 .. DRM_MAX_PEERS and row_offset >= 0");
+    if (int rc = drm::args_fk_rnea_put(tree, chain, q, qd, B, tau, pos, quat, put)) return rc;
     if (int rc = drm_fk_rnea(tree, chain, target_op, q, qd, qdd, B, flags, tau, pos, quat, scratch, stream)) return rc;
     if (!put || B == 0) return DRM_OK;
     const int n = tree->n_dofs;
@@ -758,8 +670,7 @@ int drm_fk_rnea_put(const drm_walk *tree, const drm_walk *chain, int32_t target_
 }
 
 int drm_crba(const drm_walk *w, const float *q, int64_t B, float *H, float *, void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (B < 0 || !q || !H) return fail(DRM_ERR_INVALID, "bad batch or NULL q / H");
+    if (int rc = drm::args_crba(w, q, B, H)) return rc;
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { crba_loop(w, q + b0 * n, rows, H + b0 * n * n); });
     return DRM_OK;
@@ -767,8 +678,7 @@ int drm_crba(const drm_walk *w, const float *q, int64_t B, float *H, float *, vo
 
 int drm_forward_dynamics(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int32_t flags, float *qdd,
                          float *, void *) {
-    if (int rc = rnea_checked(w, q, qd, qdd, B)) return rc;
-    if (!f) return fail(DRM_ERR_INVALID, "f must not be NULL");
+    if (int rc = drm::args_forward_dynamics(w, q, qd, f, B, qdd)) return rc;
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         fd_loop(w, q + b0 * n, qd + b0 * n, f + b0 * n, rows, flags, qdd + b0 * n);
@@ -783,11 +693,7 @@ int64_t drm_forward_dynamics_rollout_scratch_floats_aligned(const drm_walk *, in
 
 int drm_forward_dynamics_rollout(const drm_walk *w, const float *q0, const float *qd0, const float *tau, int64_t B, int32_t T, float dt,
                                  int32_t flags, float *q_traj, float *qd_traj, float *qdd_traj, float *, void *) {
-    if (int rc = check_walk(w)) return rc;
-    if (!q0 || !qd0 || !tau || !q_traj || !qd_traj) return fail(DRM_ERR_INVALID, "q0 / qd0 / tau / q_traj / qd_traj must not be NULL");
-    if (T < 1) return fail(DRM_ERR_INVALID, "a rollout takes at least one step (T = %ld)", (long)T);
-    if (!(dt > 0.0f) || !std::isfinite(dt)) return fail(DRM_ERR_INVALID, "dt must be finite and positive");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_forward_dynamics_rollout(w, q0, qd0, tau, B, T, dt, q_traj, qd_traj)) return rc;
     const int n = w->n_dofs, fd_flags = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
     const bool expl = (flags & DRM_ROLLOUT_EXPLICIT_EULER) != 0;
     const int64_t slab = B * n;
@@ -816,17 +722,9 @@ int64_t drm_inverse_kinematics_scratch_floats_aligned(const drm_walk *, int64_t)
 int drm_inverse_kinematics(const drm_walk *w, const float *q0, const float *target_pos, const float *target_quat, int64_t B,
                            int32_t max_iters, float damping, float step, float tol_pos, float tol_rot, const float *lower,
                            const float *upper, int32_t flags, float *q, float *err, int32_t *iters, float *, void *) {
-    if (int rc = check_walk(w)) return rc;
+    if (int rc = drm::args_inverse_kinematics(w, q0, target_pos, target_quat, B, max_iters, damping, step, tol_pos, tol_rot, lower, upper, flags, q, err))
+        return rc;
     const bool pos_only = (flags & DRM_IK_POSITION_ONLY) != 0;
-    if (!q0 || !target_pos || !q || !err) return fail(DRM_ERR_INVALID, "q0 / target_pos / q / err must not be NULL");
-    if ((target_quat == nullptr) != pos_only) return fail(DRM_ERR_INVALID, "target_quat must be NULL iff DRM_IK_POSITION_ONLY");
-    if ((lower == nullptr) != (upper == nullptr)) return fail(DRM_ERR_INVALID, "lower and upper must be given together");
-    if (max_iters < 0) return fail(DRM_ERR_INVALID, "max_iters must be >= 0");
-    if (!(damping > 0.0f) || !std::isfinite(damping) || !(step > 0.0f) || !std::isfinite(step))
-        return fail(DRM_ERR_INVALID, "damping and step must be finite and positive");
-    if (!(tol_pos >= 0.0f) || !std::isfinite(tol_pos) || !(tol_rot >= 0.0f) || !std::isfinite(tol_rot))
-        return fail(DRM_ERR_INVALID, "tolerances must be finite and >= 0");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     const int n = w->n_dofs;
     const drm::IkOpts o = {damping * damping, step, tol_pos, tol_rot};
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
@@ -867,13 +765,7 @@ int64_t drm_operational_space_scratch_floats_aligned(const drm_walk *, const drm
 
 int drm_operational_space(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, int64_t B, int32_t flags, float reg,
                           float *inertia, float *jbar, float *bias_acc, float *bias_force, float *, void *) {
-    if (int rc = check_walk(tree)) return rc;
-    if (int rc = check_walk(chain)) return rc;
-    if (tree->n_dofs != chain->n_dofs) return fail(DRM_ERR_INVALID, "the two walks belong to different robots");
-    if (!inertia && !jbar && !bias_acc && !bias_force) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (!q || (!qd && (bias_acc || bias_force))) return fail(DRM_ERR_INVALID, "q must not be NULL, nor qd when bias_acc / bias_force are asked for");
-    if (!(reg >= 0.0f) || !std::isfinite(reg)) return fail(DRM_ERR_INVALID, "reg must be finite and >= 0");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_operational_space(tree, chain, q, qd, B, reg, inertia, jbar, bias_acc, bias_force)) return rc;
     const bool pos_only = (flags & DRM_OSC_POSITION_ONLY) != 0;
     const float *qd_used = bias_acc || bias_force ? qd : nullptr;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
@@ -890,10 +782,7 @@ int64_t drm_forward_dynamics_derivatives_scratch_floats_aligned(const drm_walk *
 
 int drm_forward_dynamics_derivatives(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int32_t flags,
                                      float *qdd, float *dq, float *dqd, float *minv, float *, void *) {
-    if (int rc = check_backward_walk(w, 0)) return rc;
-    if (!q || !qd || !f) return fail(DRM_ERR_INVALID, "q / qd / f must not be NULL");
-    if (!qdd || !dq || !dqd || !minv) return fail(DRM_ERR_INVALID, "qdd / dqdd_dq / dqdd_dqd / minv must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_forward_dynamics_derivatives(w, q, qd, f, B, qdd, dq, dqd, minv)) return rc;
     const int fl = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { fdd_host_rows(w, q, qd, f, b0, rows, fl, qdd, dq, dqd, minv); });
     return DRM_OK;
@@ -906,11 +795,7 @@ int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *, int64_t) { r
 
 int drm_rnea_regressor(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y, float *,
                        void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if ((int64_t)w->n_dofs * (drm::REG_COLS * (int64_t)w->n_ops + w->n_dofs) >= (1 << 24))
-        return fail(DRM_ERR_UNSUPPORTED, "a row of the regressor of this walk has 2^24 entries or more (%ld ops, %ld DoFs)", w->n_ops, w->n_dofs);
-    if (!q || !qd || !Y) return fail(DRM_ERR_INVALID, "q / qd / Y must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_rnea_regressor(w, q, qd, B, Y)) return rc;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { regressor_host_rows(w, q, qd, qdd, b0, rows, flags, Y); });
     return DRM_OK;
 }
@@ -922,10 +807,7 @@ int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *, int64_t
 
 int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t, float *H, float *C, float *g, float *,
                             void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
-    if (!H && !C && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_sweep_q_qd(w, q, qd, B, H || C || g)) return rc;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { lagrangian_host_rows(w, q, qd, b0, rows, H, C, g); });
     return DRM_OK;
 }
@@ -937,10 +819,7 @@ int64_t drm_rnea_derivatives_scratch_floats_aligned(const drm_walk *, int64_t) {
 
 int drm_rnea_derivatives(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *tau, float *dq,
                          float *dqd, float *H, float *, void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q || !qd || !qdd) return fail(DRM_ERR_INVALID, "q / qd / qdd must not be NULL");
-    if (!tau && !dq && !dqd && !H) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_rnea_derivatives(w, q, qd, qdd, B, tau, dq, dqd, H)) return rc;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { idd_host_rows(w, q, qd, qdd, b0, rows, flags, tau, dq, dqd, H); });
     return DRM_OK;
 }
@@ -951,10 +830,7 @@ int64_t drm_energy_scratch_floats_aligned(const drm_walk *, int64_t) { return 0;
 
 int drm_energy(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t, float *T, float *V, float *p, float *dT, float *g,
                float *, void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
-    if (!T && !V && !p && !dT && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = drm::args_sweep_q_qd(w, q, qd, B, T || V || p || dT || g)) return rc;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { energy_host_rows(w, q, qd, b0, rows, T, V, p, dT, g); });
     return DRM_OK;
 }
@@ -968,11 +844,7 @@ int64_t drm_external_torques_scratch_floats_aligned(const drm_walk *, int64_t) {
 
 int drm_link_motion(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t T, int32_t flags, float *pos,
                     float *lv, float *av, float *la, float *aa, float *, void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-    if (!pos && !lv && !av && !la && !aa) return fail(DRM_ERR_INVALID, "every output is NULL");
+    if (int rc = drm::args_link_motion(w, q, B, T, pos, lv, av, la, aa)) return rc;
     const int mode = (la || aa) ? 2 : (lv || av) ? 1 : 0;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         if (mode == 2) link_motion_host_rows<2>(w, q, qd, qdd, b0, rows, T, flags, pos, lv, av, la, aa);
@@ -984,12 +856,7 @@ int drm_link_motion(const drm_walk *w, const float *q, const float *qd, const fl
 
 int drm_external_torques(const drm_walk *w, const float *q, const float *force, const float *torque, int64_t B, int32_t T, int32_t flags,
                          float *tau, float *, void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
-    if (!tau) return fail(DRM_ERR_INVALID, "tau must not be NULL");
+    if (int rc = drm::args_external_torques(w, q, force, torque, B, T, tau)) return rc;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { link_torques_host_rows(w, q, force, torque, b0, rows, T, flags, tau); });
     return DRM_OK;
 }
@@ -998,13 +865,7 @@ int64_t drm_link_power_dq_scratch_floats(const drm_walk *, int64_t) { return 0; 
 int64_t drm_link_power_dq_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
 int drm_link_power_dq(const drm_walk *w, const float *q, const float *qd, const float *force, const float *torque, int64_t B, int32_t T,
                       int32_t flags, float *dq, float *tau, float *, void *) {
-    if (int rc = check_sweep_walk(w)) return rc;
-    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-    if (!qd) return fail(DRM_ERR_INVALID, "qd must not be NULL");
-    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
-    if (!dq) return fail(DRM_ERR_INVALID, "dq must not be NULL");
+    if (int rc = drm::args_link_power_dq(w, q, qd, force, torque, B, T, dq)) return rc;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) { link_power_dq_host_rows(w, q, qd, force, torque, b0, rows, T, flags, dq, tau); });
     return DRM_OK;
 }
@@ -1019,11 +880,8 @@ int64_t drm_contact_rollout_scratch_floats_aligned(const drm_walk *, const drm_w
 int drm_contact_torques(const drm_walk *lw, const float *q, const float *qd, int64_t B, int32_t T, const drm_contact_plane *plane,
                         const float *radius, const drm_joint_springs *springs, const float *lower, const float *upper, int32_t flags,
                         float *tau, float *force, float *moment, float *, void *) {
-    if (int rc = check_sweep_walk(lw)) return rc;
-    if (!q || !qd || !tau) return fail(DRM_ERR_INVALID, "q / qd / tau must not be NULL");
-    if (!plane) return fail(DRM_ERR_INVALID, "drm_contact_torques needs a plane");
-    ContactArgs a;
-    if (int rc = contact_check(lw, B, T, plane, radius, springs, lower, upper, a)) return rc;
+    ContactPlan a;
+    if (int rc = drm::args_contact_torques(lw, q, qd, B, T, plane, radius, springs, lower, upper, tau, a)) return rc;
     const int n = lw->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         contact_host_rows(lw, a, q + b0 * n, qd + b0 * n, nullptr, rows, T, n, flags, true, tau + b0 * n,
@@ -1037,11 +895,8 @@ int64_t drm_contact_torques_vjp_scratch_floats_aligned(const drm_walk *, int64_t
 int drm_contact_torques_vjp(const drm_walk *lw, const float *q, const float *qd, const float *grad_tau, int64_t B, int32_t T,
                             const drm_contact_plane *plane, const float *radius, const drm_joint_springs *springs, const float *lower,
                             const float *upper, int32_t flags, float *grad_q, float *grad_qd, float *, void *) {
-    if (int rc = check_sweep_walk(lw)) return rc;
-    if (!q || !qd || !grad_tau) return fail(DRM_ERR_INVALID, "q / qd / grad_tau must not be NULL");
-    if (!grad_q && !grad_qd) return fail(DRM_ERR_INVALID, "grad_q and grad_qd are both NULL");
-    ContactArgs a;
-    if (int rc = contact_check(lw, B, T, plane, radius, springs, lower, upper, a)) return rc;
+    ContactPlan a;
+    if (int rc = drm::args_contact_torques_vjp(lw, q, qd, grad_tau, B, T, plane, radius, springs, lower, upper, grad_q, grad_qd, a)) return rc;
     const int n = lw->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         contact_vjp_host_rows(lw, a, q + b0 * n, qd + b0 * n, grad_tau + b0 * n, rows, T, n, flags, grad_q ? grad_q + b0 * n : nullptr,
@@ -1060,16 +915,7 @@ int drm_collision_cost(const drm_walk *w, const float *q, int64_t B, int32_t T, 
                        const drm_collision_world *world, const drm_collision_pairs *pairs, const drm_collision_params *params, int32_t flags,
                        float *cost, float *dq, float *, void *) {
     drm::CollTables t;
-    if (int rc = collision_check(w, q, B, T, spheres, world, pairs, t)) return rc;
-    if (!world && !pairs) return fail(DRM_ERR_INVALID, "neither a world nor pairs");
-    if (!params) return fail(DRM_ERR_INVALID, "params must not be NULL");
-    if (!cost && !dq) return fail(DRM_ERR_INVALID, "cost and dq are both NULL");
-    if (world && !drm::coll_law_ok(params->world_weight, params->world_activation))
-        return fail(DRM_ERR_INVALID, "the world weight must be finite and >= 0, its activation distance finite and > 0");
-    if (pairs && !drm::coll_law_ok(params->self_weight, params->self_activation))
-        return fail(DRM_ERR_INVALID, "the self weight must be finite and >= 0, its activation distance finite and > 0");
-    if (world) t.world = drm::coll_law_make(params->world_weight, params->world_activation);
-    if (pairs) t.self = drm::coll_law_make(params->self_weight, params->self_activation);
+    if (int rc = drm::args_collision_cost(w, q, B, T, spheres, world, pairs, params, cost, dq, t)) return rc;
     const int n = w->n_dofs;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         collision_host_rows(w, t, q + b0 * n, rows, flags, cost ? cost + b0 : nullptr, dq ? dq + b0 * n : nullptr, nullptr, nullptr, nullptr);
@@ -1081,8 +927,7 @@ int drm_sphere_distances(const drm_walk *w, const float *q, int64_t B, int32_t T
                          const drm_collision_world *world, const drm_collision_pairs *pairs, int32_t flags, float *center, float *wd,
                          float *sd, float *, void *) {
     drm::CollTables t;
-    if (int rc = collision_check(w, q, B, T, spheres, world, pairs, t)) return rc;
-    if (!center && !wd && !sd) return fail(DRM_ERR_INVALID, "every output is NULL");
+    if (int rc = drm::args_sphere_distances(w, q, B, T, spheres, world, pairs, center, wd, sd, t)) return rc;
     const int n = w->n_dofs, S = t.S;
     for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
         collision_host_rows(w, t, q + b0 * n, rows, flags, nullptr, nullptr, center ? center + b0 * S * 3 : nullptr, wd ? wd + b0 * S : nullptr,
@@ -1095,13 +940,8 @@ int drm_contact_rollout(const drm_walk *dw, const drm_walk *lw, const float *q0,
                         float dt, int32_t flags, int32_t TL, const drm_contact_plane *plane, const float *radius,
                         const drm_joint_springs *springs, const float *lower, const float *upper, float *q_traj, float *qd_traj,
                         float *qdd_traj, float *, void *) {
-    if (int rc = check_walk(dw)) return rc;
-    if (!q0 || !qd0 || !tau || !q_traj || !qd_traj) return fail(DRM_ERR_INVALID, "q0 / qd0 / tau / q_traj / qd_traj must not be NULL");
-    if (T < 1) return fail(DRM_ERR_INVALID, "a rollout takes at least one step (T = %ld)", (long)T);
-    if (!(dt > 0.0f) || !std::isfinite(dt)) return fail(DRM_ERR_INVALID, "dt must be finite and positive");
-    ContactArgs a;
-    if (int rc = contact_check(lw, B, TL, plane, radius, springs, lower, upper, a)) return rc;
-    if (plane && lw->n_dofs != dw->n_dofs) return fail(DRM_ERR_INVALID, "the two walks are not of one robot");
+    ContactPlan a;
+    if (int rc = drm::args_contact_rollout(dw, lw, q0, qd0, tau, B, T, dt, TL, plane, radius, springs, lower, upper, q_traj, qd_traj, a)) return rc;
     const int n = dw->n_dofs, fd_flags = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);
     const bool expl = (flags & DRM_ROLLOUT_EXPLICIT_EULER) != 0;
     const int64_t slab = B * n;
@@ -1139,9 +979,7 @@ int64_t drm_rnea_backward_scratch_floats(int64_t B, int32_t capacity, int32_t, i
 
 int drm_fk_backward(const drm_walk *w, const float *q, int64_t B, int32_t T, const float *gpos, const float *grot, uint64_t mask,
                     float *gq, float *gops, float *scratch, void *) {
-    if (int rc = check_backward_walk(w, mask)) return rc;
-    if (B < 0 || T < 1 || !q || !gpos) return fail(DRM_ERR_INVALID, "bad batch / target count or NULL q / grad_pos");
-    if ((mask != 0) != (gops != nullptr)) return fail(DRM_ERR_INVALID, "grad_ops_f must be given iff param_mask != 0");
+    if (int rc = drm::args_fk_backward(w, q, B, T, gpos, mask, gq, gops)) return rc;
     if (mask && !scratch) return fail(DRM_ERR_INVALID, "scratch must not be NULL (drm_fk_backward_scratch_floats)");
     const int n = w->n_dofs, entries = w->capacity * DRM_OPF_STRIDE;
     for_chunks(B, [&](int64_t c, int64_t b0, int64_t rows) {
@@ -1154,9 +992,7 @@ int drm_fk_backward(const drm_walk *w, const float *q, int64_t B, int32_t T, con
 
 int drm_fk_jacobian_backward(const drm_walk *w, const float *q, int64_t B, const float *gpos, const float *grot, const float *glin,
                              const float *gang, uint64_t mask, float *gq, float *gops, float *scratch, void *) {
-    if (int rc = check_backward_walk(w, mask)) return rc;
-    if (B < 0 || !q || !glin || !gang) return fail(DRM_ERR_INVALID, "bad batch or NULL q / grad_lin_jac / grad_ang_jac");
-    if ((mask != 0) != (gops != nullptr)) return fail(DRM_ERR_INVALID, "grad_ops_f must be given iff param_mask != 0");
+    if (int rc = drm::args_fk_jacobian_backward(w, q, B, glin, gang, mask, gq, gops)) return rc;
     if (mask && !scratch) return fail(DRM_ERR_INVALID, "scratch must not be NULL (drm_fk_backward_scratch_floats)");
     const int n = w->n_dofs, entries = w->capacity * DRM_OPF_STRIDE;
     for_chunks(B, [&](int64_t c, int64_t b0, int64_t rows) {
@@ -1170,9 +1006,8 @@ int drm_fk_jacobian_backward(const drm_walk *w, const float *q, int64_t B, const
 // forward pose, loss and adjoints chunk by chunk (any single-target walk, any B: the host build has no tile shape to respect)
 int drm_fk_mse(const drm_walk *w, const float *q, const float *target, int64_t B, uint64_t mask, float *loss, float *gq, float *gops,
                float *scratch, void *) {
-    if (int rc = check_backward_walk(w, mask)) return rc;
-    if (B < 1 || !q || !target || !loss || !scratch) return fail(DRM_ERR_INVALID, "bad batch or NULL q / target / loss / scratch");
-    if ((mask != 0) != (gops != nullptr)) return fail(DRM_ERR_INVALID, "grad_ops_f must be given iff param_mask != 0");
+    if (int rc = drm::args_fk_mse(w, q, target, mask, loss, gops, scratch)) return rc;
+    if (B < 1) return fail(DRM_ERR_INVALID, "drm_fk_mse: the loss is a mean over at least one row");
     const int n = w->n_dofs, entries = w->capacity * DRM_OPF_STRIDE;
     const int64_t chunks = n_chunks(B), stride = entries + 2;
     const float g_scale = 2.0f / (3.0f * (float)B);
@@ -1206,11 +1041,7 @@ int drm_fk_mse(const drm_walk *w, const float *q, const float *target, int64_t B
 
 int drm_rnea_backward(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, const float *gtau,
                       uint64_t mask, float *gq, float *gqd, float *gqdd, float *gops, float *scratch, void *) {
-    if (int rc = check_backward_walk(w, mask)) return rc;
-    if (B < 0 || !q || !qd || !gtau) return fail(DRM_ERR_INVALID, "bad batch or NULL q / qd / grad_tau");
-    if ((gq != nullptr) != (gqd != nullptr) || (gq != nullptr) != (gqdd != nullptr))
-        return fail(DRM_ERR_INVALID, "grad_q / grad_qd / grad_qdd: all three or none");
-    if ((mask != 0) != (gops != nullptr)) return fail(DRM_ERR_INVALID, "grad_ops_f must be given iff param_mask != 0");
+    if (int rc = drm::args_rnea_backward(w, q, qd, B, gtau, mask, gq, gqd, gqdd, gops)) return rc;
     if (mask && !scratch) return fail(DRM_ERR_INVALID, "scratch must not be NULL (drm_rnea_backward_scratch_floats)");
     const int n = w->n_dofs, entries = w->capacity * DRM_OPF_STRIDE;
     for_chunks(B, [&](int64_t c, int64_t b0, int64_t rows) {
@@ -1222,12 +1053,12 @@ int drm_rnea_backward(const drm_walk *w, const float *q, const float *qd, const 
 }
 
 int drm_link_rows(const float *params, int32_t n_links, float *rows, void *) {
-    if (n_links < 0 || !params || !rows) return fail(DRM_ERR_INVALID, "bad link count or NULL params / rows");
+    if (int rc = drm::args_link_rows(params, n_links, rows)) return rc;
     for (int i = 0; i < n_links; ++i) link_row(params + i * LINK_PARAM_FLOATS, rows + i * DRM_OPF_STRIDE);
     return DRM_OK;
 }
 int drm_link_rows_backward(const float *params, const float *grad_rows, int32_t n_links, float *grad_params, void *) {
-    if (n_links < 0 || !params || !grad_rows || !grad_params) return fail(DRM_ERR_INVALID, "bad link count or NULL argument");
+    if (int rc = drm::args_link_rows_backward(params, grad_rows, n_links, grad_params)) return rc;
     for (int i = 0; i < n_links; ++i)
         link_row_backward(params + i * LINK_PARAM_FLOATS, grad_rows + i * DRM_OPF_STRIDE, grad_params + i * LINK_PARAM_FLOATS);
     return DRM_OK;
@@ -1235,23 +1066,19 @@ int drm_link_rows_backward(const float *params, const float *grad_rows, int32_t 
 
 int drm_walk_table(const float *params, int32_t n_links, const float *base, const int32_t *sel, const float *gsign, int32_t n_entries,
                    float *ops_f, void *) {
-    if (n_links < 1 || n_links > 32 || n_entries < 0 || n_entries > DRM_MAX_OPS * DRM_OPF_STRIDE)
-        return fail(DRM_ERR_INVALID, "drm_walk_table takes 1 .. 32 links and at most %ld entries (%ld)", DRM_MAX_OPS * DRM_OPF_STRIDE, n_entries);
-    if (!params || !base || !sel || !gsign || !ops_f) return fail(DRM_ERR_INVALID, "NULL argument");
+    if (int rc = drm::args_walk_table("drm_walk_table", params, n_links, base, sel, gsign, n_entries, ops_f)) return rc;
     float rows[32 * DRM_OPF_STRIDE];
     for (int i = 0; i < n_links; ++i) link_row(params + i * LINK_PARAM_FLOATS, rows + i * DRM_OPF_STRIDE);
     for (int e = 0; e < n_entries; ++e) {
         const int r = sel[e];
-        if (r >= n_links * DRM_OPF_STRIDE) return fail(DRM_ERR_INVALID, "sel[%ld] = %ld is beyond the learnable rows", e, r);
+        if (r >= n_links * DRM_OPF_STRIDE) return fail(DRM_ERR_INVALID, "sel[%s%ld] = %ld is beyond the learnable rows", "", e, r);
         ops_f[e] = r >= 0 ? rows[r] * gsign[e] : base[e];
     }
     return DRM_OK;
 }
 int drm_walk_table_backward(const float *params, int32_t n_links, const float *grad_ops_f, const int32_t *sel, const float *gsign,
                             int32_t n_entries, float *grad_params, void *) {
-    if (n_links < 1 || n_links > 32 || n_entries < 0 || n_entries > DRM_MAX_OPS * DRM_OPF_STRIDE)
-        return fail(DRM_ERR_INVALID, "drm_walk_table_backward takes 1 .. 32 links and at most %ld entries (%ld)", DRM_MAX_OPS * DRM_OPF_STRIDE, n_entries);
-    if (!params || !grad_ops_f || !sel || !gsign || !grad_params) return fail(DRM_ERR_INVALID, "NULL argument");
+    if (int rc = drm::args_walk_table("drm_walk_table_backward", params, n_links, grad_ops_f, sel, gsign, n_entries, grad_params)) return rc;
     float grows[32 * DRM_OPF_STRIDE];
     for (int r = 0; r < n_links * DRM_OPF_STRIDE; ++r) grows[r] = 0.0f;
     for (int e = 0; e < n_entries; ++e) { // entry order, as the kernel adds them
@@ -1265,20 +1092,11 @@ int drm_walk_table_backward(const float *params, int32_t n_links, const float *g
 
 // ABI 13: the table from the links' parameter tensors where they lie, in the forms their modules store them, and the gradient back
 // to those tensors (include/drm_hip.h)
-static int links_raw(const char *, const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links, int32_t n_entries,
-                     float *raw, int32_t (*form)[3], float (*c)[3]) {
-    if (!links) return fail(DRM_ERR_INVALID, "drm_walk_table_links: links must not be NULL");
-    if (n_links < 1 || n_links > 32 || n_entries < 1 || n_entries > DRM_MAX_OPS * DRM_OPF_STRIDE)
-        return fail(DRM_ERR_INVALID, "drm_walk_table_links: 1..32 learnable links and at most 32 x 32 walk entries (%ld, %ld)", n_links, n_entries);
+// the pieces and forms of CHECKED links (drm_args.hpp args_walk_table_links) read into drm_link_rows' layout
+static void links_raw(const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links, float *raw, int32_t (*form)[3], float (*c)[3]) {
     for (int l = 0; l < n_links; ++l) {
         const float *at[6] = {links[l].rot_angles, links[l].trans, links[l].mass, links[l].com, links[l].inertia_mat, links[l].damping};
-        for (int j = 0; j < 6; ++j)
-            if (!at[j]) return fail(DRM_ERR_INVALID, "drm_walk_table_links: a piece of link %ld is NULL", l);
         const drm_link_forms f = forms ? forms[l] : drm_link_forms{};
-        const bool ok = (f.mass == DRM_FORM_PLAIN || f.mass == DRM_FORM_SQUARE_PLUS) &&
-                        (f.damping == DRM_FORM_PLAIN || f.damping == DRM_FORM_SQUARE_PLUS) &&
-                        (f.inertia_mat == DRM_FORM_PLAIN || (f.inertia_mat >= DRM_FORM_SYMM && f.inertia_mat <= DRM_FORM_COV));
-        if (!ok) return fail(DRM_ERR_INVALID, "drm_walk_table_links: unknown form of a piece of link %ld", l);
         form[l][0] = f.mass; form[l][1] = f.inertia_mat; form[l][2] = f.damping;
         c[l][0] = f.mass_c; c[l][1] = f.inertia_mat_c; c[l][2] = f.damping_c;
         for (int k = 0; k < LINK_PARAM_FLOATS; ++k) {
@@ -1287,13 +1105,13 @@ static int links_raw(const char *, const drm_link_pieces *links, const drm_link_
             raw[l * LINK_PARAM_FLOATS + k] = there ? at[piece][off] : 0.0f;
         }
     }
-    return DRM_OK;
 }
 int drm_walk_table_links(const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links, const float *base, const int32_t *sel,
                          const float *gsign, int32_t n_entries, float *ops_f, void *) {
     float raw[32 * LINK_PARAM_FLOATS], params[32 * LINK_PARAM_FLOATS], c[32][3];
     int32_t form[32][3];
-    if (int rc = links_raw("drm_walk_table_links", links, forms, n_links, n_entries, raw, form, c)) return rc;
+    if (int rc = drm::args_walk_table_links("drm_walk_table_links", links, forms, n_links, base, sel, gsign, n_entries, ops_f)) return rc;
+    links_raw(links, forms, n_links, raw, form, c);
     for (int l = 0; l < n_links; ++l) link_forms_apply(form[l], c[l], raw + l * LINK_PARAM_FLOATS, params + l * LINK_PARAM_FLOATS);
     return drm_walk_table(params, n_links, base, sel, gsign, n_entries, ops_f, nullptr);
 }
@@ -1301,7 +1119,9 @@ int drm_walk_table_links_backward(const drm_link_pieces *links, const drm_link_f
                                   const int32_t *sel, const float *gsign, int32_t n_entries, float *grad_params, void *) {
     float raw[32 * LINK_PARAM_FLOATS], params[32 * LINK_PARAM_FLOATS], c[32][3];
     int32_t form[32][3];
-    if (int rc = links_raw("drm_walk_table_links_backward", links, forms, n_links, n_entries, raw, form, c)) return rc;
+    if (int rc = drm::args_walk_table_links("drm_walk_table_links_backward", links, forms, n_links, grad_ops_f, sel, gsign, n_entries, grad_params))
+        return rc;
+    links_raw(links, forms, n_links, raw, form, c);
     for (int l = 0; l < n_links; ++l) link_forms_apply(form[l], c[l], raw + l * LINK_PARAM_FLOATS, params + l * LINK_PARAM_FLOATS);
     if (int rc = drm_walk_table_backward(params, n_links, grad_ops_f, sel, gsign, n_entries, grad_params, nullptr)) return rc;
     for (int l = 0; l < n_links; ++l) link_forms_grad(form[l], raw + l * LINK_PARAM_FLOATS, grad_params + l * LINK_PARAM_FLOATS);
@@ -1312,15 +1132,10 @@ int drm_walk_table_links_backward(const drm_link_pieces *links, const drm_link_f
 // gradient back through the table's map
 int drm_fk_mse_links(const drm_walk *w, const int32_t *sel, const float *gsign, const drm_link_pieces *links, int32_t n_links, const float *q,
                      const float *target, int64_t B, uint64_t mask, float *loss, float *gq, float *grad_params, float *scratch, void *) {
-    if (int rc = check_backward_walk(w, mask)) return rc;
-    if (!sel || !gsign || !links || !grad_params) return fail(DRM_ERR_INVALID, "NULL sel / gsign / links / grad_params");
-    if (n_links < 1 || n_links > DRM_FK_MSE_MAX_LINKS)
-        return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse_links takes 1 .. %ld learnable links (%ld)", DRM_FK_MSE_MAX_LINKS, n_links);
-    if (!mask) return fail(DRM_ERR_INVALID, "param_mask must select the ops of the learnable links");
+    if (int rc = drm::args_fk_mse_links(w, sel, gsign, links, n_links, q, target, mask, loss, grad_params, scratch)) return rc;
     const int entries = w->capacity * DRM_OPF_STRIDE;
     float params[DRM_FK_MSE_MAX_LINKS * LINK_PARAM_FLOATS] = {0.0f};
     for (int l = 0; l < n_links; ++l) {
-        if (!links[l].rot_angles || !links[l].trans) return fail(DRM_ERR_INVALID, "rot_angles / trans of a link are NULL");
         for (int i = 0; i < 3; ++i) {
             params[l * LINK_PARAM_FLOATS + i] = links[l].rot_angles[i];
             params[l * LINK_PARAM_FLOATS + 3 + i] = links[l].trans[i];

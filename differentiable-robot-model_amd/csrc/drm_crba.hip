@@ -11,6 +11,7 @@
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
 #include "drm_static.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -404,10 +405,8 @@ extern "C" int64_t drm_crba_scratch_floats(const drm_walk *w, int64_t B) { retur
 extern "C" int64_t drm_crba_scratch_floats_aligned(const drm_walk *w, int64_t B) { return drm_crba_scratch_floats_impl(w, B, true); }
 
 extern "C" int drm_crba(const drm_walk *w, const float *q, int64_t B, float *H, float *scratch, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_crba(w, q, B, H);
     if (rc) return rc;
-    if (!q || !H) return fail(DRM_ERR_INVALID, "q / H must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs, nn = n * n;
     hipStream_t s = (hipStream_t)stream;

@@ -20,6 +20,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_energy.hpp"
 #include "drm_rows.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -148,18 +149,15 @@ static void launch_energy_arm(const drm_walk *w, const float *q, const float *qd
 using namespace drm;
 
 static int64_t energy_scratch(const drm_walk *w, int64_t B, bool aligned) {
-    return rows_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, energy_state_floats(w), ENERGY_LDS_BYTES);
+    return check_sweep_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, energy_state_floats(w), ENERGY_LDS_BYTES);
 }
 extern "C" int64_t drm_energy_scratch_floats(const drm_walk *w, int64_t B) { return energy_scratch(w, B, false); }
 extern "C" int64_t drm_energy_scratch_floats_aligned(const drm_walk *w, int64_t B) { return energy_scratch(w, B, true); }
 
 extern "C" int drm_energy(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t flags, float *T, float *V, float *p,
                           float *dT, float *g, float *scratch, void *stream) {
-    int rc = rows_check_walk(w);
+    int rc = args_sweep_q_qd(w, q, qd, B, T || V || p || dT || g);
     if (rc) return rc;
-    if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
-    if (!T && !V && !p && !dT && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;

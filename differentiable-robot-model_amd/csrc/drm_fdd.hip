@@ -23,6 +23,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_fdd.hpp"
 #include "drm_sample.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -342,23 +343,12 @@ static FddScratch fdd_scratch_layout(const drm_walk *w, int64_t rows) {
     return s;
 }
 
-// the walks drm_rnea_backward takes
-static int fdd_check_walk(const drm_walk *w) {
-    int rc = check_walk(w);
-    if (rc) return rc;
-    if (w->capacity > DRM_MAX_OPS)
-        return fail(DRM_ERR_UNSUPPORTED, "backward walks take at most %s%ld ops (capacity %ld)", "", (long)DRM_MAX_OPS, (long)w->capacity);
-    if (w->n_slots > DRM_MAX_SLOTS_BACKWARD)
-        return fail(DRM_ERR_UNSUPPORTED, "backward walks take at most %s%ld save slots (%ld)", "", (long)DRM_MAX_SLOTS_BACKWARD, (long)w->n_slots);
-    return DRM_OK;
-}
-
 } // namespace drm
 
 using namespace drm;
 
 static int64_t fdd_scratch_floats_impl(const drm_walk *w, int64_t B, bool aligned) {
-    if (fdd_check_walk(w) || B <= 0) return 0;
+    if (check_backward_walk(w) || B <= 0) return 0;
     const int64_t lo = fdd_fused(w, B, aligned) ? B / WAVE * WAVE : 0;
     if (lo == B) return 0;
     return fdd_scratch_layout(w, B - lo).total;
@@ -370,11 +360,8 @@ extern "C" int64_t drm_forward_dynamics_derivatives_scratch_floats_aligned(const
 
 extern "C" int drm_forward_dynamics_derivatives(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B, int32_t flags,
                                                 float *qdd, float *dq, float *dqd, float *minv, float *scratch, void *stream) {
-    int rc = fdd_check_walk(w);
+    int rc = args_forward_dynamics_derivatives(w, q, qd, f, B, qdd, dq, dqd, minv);
     if (rc) return rc;
-    if (!q || !qd || !f) return fail(DRM_ERR_INVALID, "q / qd / f must not be NULL");
-    if (!qdd || !dq || !dqd || !minv) return fail(DRM_ERR_INVALID, "qdd / dqdd_dq / dqdd_dqd / minv must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs, dyn_flags = flags & (DRM_RNEA_GRAVITY | DRM_RNEA_DAMPING);

@@ -8,6 +8,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -289,11 +290,8 @@ __global__ void __launch_bounds__(WAVE * 4)
 using namespace drm;
 
 extern "C" int drm_fk_links(const drm_walk *w, const float *q, int64_t B, int32_t n_targets, float *pos, float *quat, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_fk(w, q, B, n_targets, pos, quat);
     if (rc) return rc;
-    if (!q || !pos || !quat) return fail(DRM_ERR_INVALID, "q / pos / quat must not be NULL");
-    if (B < 0 || n_targets < 1) return fail(DRM_ERR_INVALID, "negative batch or no targets");
-    if (n_targets > w->n_ops) return fail(DRM_ERR_INVALID, "more targets than ops in the walk");
     if (B == 0) return DRM_OK;
     if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
     const int n = w->n_dofs, T = n_targets;
@@ -325,17 +323,11 @@ extern "C" int drm_fk_links(const drm_walk *w, const float *q, int64_t B, int32_
 
 extern "C" int drm_fk_fanout(const drm_walk *chains, int32_t n_chains, const float *q, int64_t B, float *pos, float *quat,
                              void *stream) {
-    if (!chains || n_chains < 2 || n_chains > 4) return fail(DRM_ERR_INVALID, "fan-out FK takes 2 to 4 chains");
-    if (!q || !pos || !quat) return fail(DRM_ERR_INVALID, "q / pos / quat must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
+    if (int rc = args_fk_fanout(chains, n_chains, q, B, pos, quat)) return rc;
     FanoutTables tab;
     int max_ops = 1;
     for (int t = 0; t < 4; ++t) {
         const drm_walk *w = chains + (t < n_chains ? t : 0);
-        int rc = check_walk(w);
-        if (rc) return rc;
-        if (w->capacity != chains[0].capacity || w->n_dofs != chains[0].n_dofs || w->n_slots != 0)
-            return fail(DRM_ERR_INVALID, "fan-out chains must share capacity and n_dofs and have no branch points");
         if (!table_aligned(w)) return fail(DRM_ERR_INVALID, "ops_f must be 16-byte aligned");
         tab.ops_f[t] = w->ops_f;
         tab.ops_i[t] = w->ops_i;
@@ -368,11 +360,8 @@ extern "C" int drm_fk_fanout(const drm_walk *chains, int32_t n_chains, const flo
 
 extern "C" int drm_fk(const drm_walk *w, const float *q, int64_t B, int32_t n_targets, float *pos, float *quat,
                       void *stream) {
-    int rc = check_walk(w);
+    int rc = args_fk(w, q, B, n_targets, pos, quat);
     if (rc) return rc;
-    if (!q || !pos || !quat) return fail(DRM_ERR_INVALID, "q / pos / quat must not be NULL");
-    if (B < 0 || n_targets < 1) return fail(DRM_ERR_INVALID, "negative batch or no targets");
-    if (n_targets > w->n_ops) return fail(DRM_ERR_INVALID, "more targets than ops in the walk");
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs, T = n_targets;
     if (T == 1 && w->n_ops >= 1) {
@@ -451,15 +440,7 @@ extern "C" int drm_fk(const drm_walk *w, const float *q, int64_t B, int32_t n_ta
 
 extern "C" int drm_fk_fanout_links(const drm_walk *chains, int32_t n_chains, const float *q, int64_t B, float *pos, float *quat,
                                    void *stream) {
-    if (!chains || n_chains < 2 || n_chains > 4) return fail(DRM_ERR_INVALID, "fan-out FK takes 2 to 4 chains");
-    if (!q || !pos || !quat) return fail(DRM_ERR_INVALID, "q / pos / quat must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    for (int t = 0; t < n_chains; ++t) {
-        int rc = check_walk(chains + t);
-        if (rc) return rc;
-        if (chains[t].capacity != chains[0].capacity || chains[t].n_dofs != chains[0].n_dofs || chains[t].n_slots != 0)
-            return fail(DRM_ERR_INVALID, "fan-out chains must share capacity and n_dofs and have no branch points");
-    }
+    if (int rc = args_fk_fanout(chains, n_chains, q, B, pos, quat)) return rc;
     if (B == 0) return DRM_OK;
     const int n = chains[0].n_dofs;
     // full tiles: a wavefront per chain, each writing its link's arrays; what is left (a ragged tail; everything when the fan-out

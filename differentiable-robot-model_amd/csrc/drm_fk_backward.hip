@@ -21,6 +21,7 @@
 #include "drm_common.hpp"
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -656,13 +657,7 @@ static int fk_backward_launch(const drm_walk *w, const float *q, int64_t B, int3
                               const float *grad_rot, const float *grad_lin, const float *grad_ang, uint64_t param_mask, float *grad_q,
                               float *grad_ops_f, float *scratch, void *stream) {
     const bool jac = grad_lin != nullptr;
-    if (B < 0 || n_targets < 1) return fail(DRM_ERR_INVALID, "negative batch or no targets");
-    if (n_targets > w->n_ops) return fail(DRM_ERR_INVALID, "more targets than ops in the walk");
-    if ((param_mask != 0) != (grad_ops_f != nullptr))
-        return fail(DRM_ERR_INVALID, "grad_ops_f must be given exactly when param_mask selects ops");
-    if (!grad_q && !grad_ops_f) return fail(DRM_ERR_INVALID, "nothing to compute: grad_q and grad_ops_f are both NULL");
     if (!scratch) return fail(DRM_ERR_INVALID, "scratch must not be NULL (drm_fk_backward_scratch_floats)");
-    if (w->capacity < 64 && (param_mask >> w->capacity)) return fail(DRM_ERR_INVALID, "param_mask selects ops beyond the walk's capacity");
     const int n = w->n_dofs, T = n_targets, cap = w->capacity;
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) {
@@ -752,12 +747,7 @@ static int fk_backward_launch(const drm_walk *w, const float *q, int64_t B, int3
 extern "C" int drm_fk_backward(const drm_walk *w, const float *q, int64_t B, int32_t n_targets, const float *grad_pos,
                                const float *grad_rot, uint64_t param_mask, float *grad_q, float *grad_ops_f, float *scratch,
                                void *stream) {
-    int rc = check_walk(w);
-    if (rc) return rc;
-    if (!q || !grad_pos) return fail(DRM_ERR_INVALID, "q / grad_pos must not be NULL");
-    if (w->n_slots > DRM_MAX_SLOTS_BACKWARD || w->capacity > DRM_MAX_OPS)
-        return fail(DRM_ERR_UNSUPPORTED, "the backward kernels take walks of up to %s%ld links and %ld save slots", "", (long)DRM_MAX_OPS,
-                    (long)DRM_MAX_SLOTS_BACKWARD);
+    if (int rc = args_fk_backward(w, q, B, n_targets, grad_pos, param_mask, grad_q, grad_ops_f)) return rc;
     return fk_backward_launch(w, q, B, n_targets, grad_pos, grad_rot, nullptr, nullptr, param_mask, grad_q, grad_ops_f, scratch,
                               stream);
 }
@@ -771,16 +761,12 @@ extern "C" int64_t drm_fk_mse_scratch_floats(int64_t B, int32_t capacity) {
 // kernel, the fixed-order reduction): see include/drm_hip.h
 extern "C" int drm_fk_mse(const drm_walk *w, const float *q, const float *target, int64_t B, uint64_t param_mask, float *loss,
                           float *grad_q, float *grad_ops_f, float *scratch, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_fk_mse(w, q, target, param_mask, loss, grad_ops_f, scratch);
     if (rc) return rc;
-    if (!q || !target || !loss || !scratch) return fail(DRM_ERR_INVALID, "q / target / loss / scratch must not be NULL");
-    if ((param_mask != 0) != (grad_ops_f != nullptr))
-        return fail(DRM_ERR_INVALID, "grad_ops_f must be given exactly when param_mask selects ops");
     const int cap = w->capacity;
     if (!(arm7_walk(w) && aligned16(q, target, grad_q, w->ops_f) && full_tiles_fit(B) && B % WAVE == 0))
         return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse takes 7-DoF arm chains (DRM_WALK_ARM_CHAIN, capacity 8), batches that are a "
                                          "multiple of 64 rows and 16-byte aligned pointers; compose drm_fk and drm_fk_backward otherwise%s", "");
-    if (param_mask >> cap) return fail(DRM_ERR_INVALID, "param_mask selects ops beyond the walk's capacity");
     hipStream_t s = (hipStream_t)stream;
     const int n_tiles = (int)(B / WAVE);
     const int waves = backward_waves(B, MAX_WAVES_PER_BLOCK);
@@ -807,21 +793,13 @@ extern "C" int drm_fk_mse(const drm_walk *w, const float *q, const float *target
 extern "C" int drm_fk_mse_links(const drm_walk *w, const int32_t *sel, const float *gsign, const drm_link_pieces *links, int32_t n_links,
                                 const float *q, const float *target, int64_t B, uint64_t param_mask, float *loss, float *grad_q,
                                 float *grad_params, float *scratch, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_fk_mse_links(w, sel, gsign, links, n_links, q, target, param_mask, loss, grad_params, scratch);
     if (rc) return rc;
-    if (!sel || !gsign || !links || !q || !target || !loss || !grad_params || !scratch)
-        return fail(DRM_ERR_INVALID, "drm_fk_mse_links: sel / gsign / links / q / target / loss / grad_params / scratch must not be NULL");
-    if (n_links < 1 || n_links > DRM_FK_MSE_MAX_LINKS)
-        return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse_links takes 1 .. %s%ld learnable links (%ld): compose drm_walk_table, drm_fk_mse, "
-                                         "drm_walk_table_backward otherwise", "", (long)DRM_FK_MSE_MAX_LINKS, (long)n_links);
-    const int cap = w->capacity;
     if (!(arm7_walk(w) && aligned16(q, target, grad_q, w->ops_f, sel, gsign) && full_tiles_fit(B) && B % WAVE == 0))
         return fail(DRM_ERR_UNSUPPORTED, "drm_fk_mse_links takes what drm_fk_mse takes: 7-DoF arm chains (capacity 8), batches that are a "
                                          "multiple of 64 rows, 16-byte aligned pointers%s", "");
-    if (!param_mask || (param_mask >> cap)) return fail(DRM_ERR_INVALID, "param_mask must select ops of the walk (those of the learnable links)");
     LinkArgs la{};
     for (int l = 0; l < n_links; ++l) {
-        if (!links[l].rot_angles || !links[l].trans) return fail(DRM_ERR_INVALID, "drm_fk_mse_links: rot_angles / trans of a link are NULL");
         la.rpy[l] = links[l].rot_angles;
         la.trans[l] = links[l].trans;
     }
@@ -848,11 +826,7 @@ extern "C" int drm_fk_mse_links(const drm_walk *w, const int32_t *sel, const flo
 extern "C" int drm_fk_jacobian_backward(const drm_walk *w, const float *q, int64_t B, const float *grad_pos,
                                         const float *grad_rot, const float *grad_lin_jac, const float *grad_ang_jac,
                                         uint64_t param_mask, float *grad_q, float *grad_ops_f, float *scratch, void *stream) {
-    int rc = check_walk(w);
-    if (rc) return rc;
-    if (!q || !grad_lin_jac || !grad_ang_jac) return fail(DRM_ERR_INVALID, "q / grad_lin_jac / grad_ang_jac must not be NULL");
-    if (w->n_slots != 0) return fail(DRM_ERR_INVALID, "the walk must be the root->link chain of the Jacobian's target (no branch points)");
-    if (w->capacity > DRM_MAX_OPS) return fail(DRM_ERR_UNSUPPORTED, "the backward kernels take walks of up to %s%ld links", "", (long)DRM_MAX_OPS);
+    if (int rc = args_fk_jacobian_backward(w, q, B, grad_lin_jac, grad_ang_jac, param_mask, grad_q, grad_ops_f)) return rc;
     return fk_backward_launch(w, q, B, 1, grad_pos, grad_rot, grad_lin_jac, grad_ang_jac, param_mask, grad_q, grad_ops_f, scratch,
                               stream);
 }

@@ -10,6 +10,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -101,11 +102,8 @@ using namespace drm;
 
 extern "C" int drm_fk_jacobian(const drm_walk *w, const float *q, int64_t B, float *pos, float *quat, float *lin_jac,
                                float *ang_jac, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_fk_jacobian(w, q, B, lin_jac, ang_jac);
     if (rc) return rc;
-    if (!q || !lin_jac || !ang_jac) return fail(DRM_ERR_INVALID, "q / lin_jac / ang_jac must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (w->target_perm < 0 || w->target_perm > 5) return fail(DRM_ERR_INVALID, "target_perm must be in 0..5");
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs;
     const uint32_t align = al16(q, AL_Q) | al16(pos, AL_POS) | al16(quat, AL_QUAT) | al16(lin_jac, AL_LIN) |

@@ -15,6 +15,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -416,10 +417,8 @@ extern "C" int64_t drm_forward_dynamics_scratch_floats_aligned(const drm_walk *w
 
 extern "C" int drm_forward_dynamics(const drm_walk *w, const float *q, const float *qd, const float *f, int64_t B,
                                     int32_t flags, float *qdd, float *scratch, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_forward_dynamics(w, q, qd, f, B, qdd);
     if (rc) return rc;
-    if (!q || !qd || !f || !qdd) return fail(DRM_ERR_INVALID, "q / qd / f / qdd must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs;
     hipStream_t s = (hipStream_t)stream;

@@ -5,6 +5,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_link_forms.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -13,21 +14,6 @@ static thread_local char g_err[512] = "";
 int fail(int code, const char *fmt, const char *a, long b, long c) {
     snprintf(g_err, sizeof(g_err), fmt, a, b, c);
     return code;
-}
-
-int check_walk(const drm_walk *w) {
-    if (!w) return fail(DRM_ERR_INVALID, "walk is NULL");
-    if (!w->ops_f || !w->ops_i) return fail(DRM_ERR_INVALID, "walk tables are NULL");
-    const int c = w->capacity;
-    if (c < 4 || (c & 3) || c > 0xffff)
-        return fail(DRM_ERR_INVALID, "walk capacity %s%ld is not a multiple of 4 in [4, 65535]", "", c);
-    if (w->n_ops < 0 || w->n_ops > c)
-        return fail(DRM_ERR_INVALID, "walk has %s%ld ops but capacity %ld", "", w->n_ops, c);
-    if (w->n_dofs < 1 || w->n_dofs > DRM_MAX_DOFS)
-        return fail(DRM_ERR_UNSUPPORTED, "n_dofs %s%ld outside [1, %ld]", "", w->n_dofs, DRM_MAX_DOFS);
-    if (w->n_slots < 0 || w->n_slots > DRM_MAX_SLOTS)
-        return fail(DRM_ERR_UNSUPPORTED, "walk needs %s%ld save slots, kernels have %ld", "", w->n_slots, DRM_MAX_SLOTS);
-    return DRM_OK;
 }
 
 int launched() {
@@ -256,72 +242,56 @@ __global__ void __launch_bounds__(WALK_TABLE_THREADS)
 extern "C" {
 int drm_walk_table(const float *params, int32_t n_links, const float *base, const int32_t *sel, const float *gsign,
                    int32_t n_entries, float *ops_f, void *stream) {
-    if (!params || !base || !sel || !gsign || !ops_f) return drm::fail(DRM_ERR_INVALID, "drm_walk_table: NULL argument");
-    if (n_links < 1 || n_links > drm::WALK_TABLE_MAX_LINKS || n_entries < 1 || n_entries > DRM_MAX_OPS * DRM_OPF_STRIDE)
-        return drm::fail(DRM_ERR_INVALID, "drm_walk_table: 1..32 learnable links and at most 32 x 32 walk entries");
+    if (int rc = drm::args_walk_table("drm_walk_table", params, n_links, base, sel, gsign, n_entries, ops_f)) return rc;
     hipLaunchKernelGGL(drm::walk_table_kernel, dim3(1), dim3(drm::WALK_TABLE_THREADS), 0, (hipStream_t)stream, params,
                        (int)n_links, base, sel, gsign, (int)n_entries, ops_f);
     return drm::launched();
 }
 int drm_walk_table_backward(const float *params, int32_t n_links, const float *grad_ops_f, const int32_t *sel,
                             const float *gsign, int32_t n_entries, float *grad_params, void *stream) {
-    if (!params || !grad_ops_f || !sel || !gsign || !grad_params)
-        return drm::fail(DRM_ERR_INVALID, "drm_walk_table_backward: NULL argument");
-    if (n_links < 1 || n_links > drm::WALK_TABLE_MAX_LINKS || n_entries < 1 || n_entries > DRM_MAX_OPS * DRM_OPF_STRIDE)
-        return drm::fail(DRM_ERR_INVALID, "drm_walk_table_backward: 1..32 learnable links and at most 32 x 32 walk entries");
+    if (int rc = drm::args_walk_table("drm_walk_table_backward", params, n_links, grad_ops_f, sel, gsign, n_entries, grad_params)) return rc;
     hipLaunchKernelGGL(drm::walk_table_backward_kernel<false>, dim3(1), dim3(drm::WALK_TABLE_THREADS), 0, (hipStream_t)stream,
                        params, (int)n_links, grad_ops_f, sel, gsign, (int)n_entries, grad_params, drm::LinkSources{});
     return drm::launched();
 }
-static int link_sources(const char *who, const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links, int32_t n_entries,
-                        drm::LinkSources &src) {
-    if (!links) return drm::fail(DRM_ERR_INVALID, "%s: links must not be NULL", who);
-    if (n_links < 1 || n_links > drm::WALK_TABLE_MAX_LINKS || n_entries < 1 || n_entries > DRM_MAX_OPS * DRM_OPF_STRIDE)
-        return drm::fail(DRM_ERR_INVALID, "%s: 1..32 learnable links and at most 32 x 32 walk entries", who);
+// the kernels' view of CHECKED links (drm_args.hpp args_walk_table_links)
+static drm::LinkSources link_sources(const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links) {
+    drm::LinkSources src{};
     for (int l = 0; l < n_links; ++l) {
         const float *at[6] = {links[l].rot_angles, links[l].trans, links[l].mass, links[l].com, links[l].inertia_mat, links[l].damping};
-        for (int j = 0; j < 6; ++j) {
-            if (!at[j]) return drm::fail(DRM_ERR_INVALID, "%s: a piece of a link is NULL", who);
-            src.at[l][j] = at[j];
-        }
+        for (int j = 0; j < 6; ++j) src.at[l][j] = at[j];
         const drm_link_forms f = forms ? forms[l] : drm_link_forms{};
-        const bool ok = (f.mass == DRM_FORM_PLAIN || f.mass == DRM_FORM_SQUARE_PLUS) &&
-                        (f.damping == DRM_FORM_PLAIN || f.damping == DRM_FORM_SQUARE_PLUS) &&
-                        (f.inertia_mat == DRM_FORM_PLAIN || (f.inertia_mat >= DRM_FORM_SYMM && f.inertia_mat <= DRM_FORM_COV));
-        if (!ok) return drm::fail(DRM_ERR_INVALID, "%s: unknown form of a piece", who);
         src.form[l][0] = f.mass; src.form[l][1] = f.inertia_mat; src.form[l][2] = f.damping;
         src.c[l][0] = f.mass_c; src.c[l][1] = f.inertia_mat_c; src.c[l][2] = f.damping_c;
     }
-    return DRM_OK;
+    return src;
 }
 int drm_walk_table_links(const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links, const float *base, const int32_t *sel,
                          const float *gsign, int32_t n_entries, float *ops_f, void *stream) {
-    if (!base || !sel || !gsign || !ops_f) return drm::fail(DRM_ERR_INVALID, "drm_walk_table_links: NULL argument");
-    drm::LinkSources src{};
-    if (int rc = link_sources("drm_walk_table_links", links, forms, n_links, n_entries, src)) return rc;
+    if (int rc = drm::args_walk_table_links("drm_walk_table_links", links, forms, n_links, base, sel, gsign, n_entries, ops_f)) return rc;
+    const drm::LinkSources src = link_sources(links, forms, n_links);
     hipLaunchKernelGGL(drm::walk_table_links_kernel, dim3(1), dim3(drm::WALK_TABLE_THREADS), 0, (hipStream_t)stream, src, (int)n_links,
                        base, sel, gsign, (int)n_entries, ops_f);
     return drm::launched();
 }
 int drm_walk_table_links_backward(const drm_link_pieces *links, const drm_link_forms *forms, int32_t n_links, const float *grad_ops_f,
                                   const int32_t *sel, const float *gsign, int32_t n_entries, float *grad_params, void *stream) {
-    if (!grad_ops_f || !sel || !gsign || !grad_params) return drm::fail(DRM_ERR_INVALID, "drm_walk_table_links_backward: NULL argument");
-    drm::LinkSources src{};
-    if (int rc = link_sources("drm_walk_table_links_backward", links, forms, n_links, n_entries, src)) return rc;
+    if (int rc = drm::args_walk_table_links("drm_walk_table_links_backward", links, forms, n_links, grad_ops_f, sel, gsign, n_entries, grad_params))
+        return rc;
+    const drm::LinkSources src = link_sources(links, forms, n_links);
     hipLaunchKernelGGL(drm::walk_table_backward_kernel<true>, dim3(1), dim3(drm::WALK_TABLE_THREADS), 0, (hipStream_t)stream,
                        (const float *)nullptr, (int)n_links, grad_ops_f, sel, gsign, (int)n_entries, grad_params, src);
     return drm::launched();
 }
 int drm_link_rows(const float *params, int32_t n_links, float *rows, void *stream) {
-    if (!params || !rows || n_links < 0) return drm::fail(DRM_ERR_INVALID, "params / rows must not be NULL, n_links >= 0");
+    if (int rc = drm::args_link_rows(params, n_links, rows)) return rc;
     if (n_links == 0) return DRM_OK;
     hipLaunchKernelGGL(drm::link_rows_kernel, dim3((unsigned)((n_links + 63) / 64)), dim3(64), 0, (hipStream_t)stream, params,
                        (int)n_links, rows);
     return drm::launched();
 }
 int drm_link_rows_backward(const float *params, const float *grad_rows, int32_t n_links, float *grad_params, void *stream) {
-    if (!params || !grad_rows || !grad_params || n_links < 0)
-        return drm::fail(DRM_ERR_INVALID, "params / grad_rows / grad_params must not be NULL, n_links >= 0");
+    if (int rc = drm::args_link_rows_backward(params, grad_rows, n_links, grad_params)) return rc;
     if (n_links == 0) return DRM_OK;
     hipLaunchKernelGGL(drm::link_rows_backward_kernel, dim3((unsigned)((n_links + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
                        params, grad_rows, (int)n_links, grad_params);

@@ -24,6 +24,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_idd.hpp"
 #include "drm_rows.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -160,18 +161,15 @@ __global__ void __launch_bounds__(WAVE)
 using namespace drm;
 
 static int64_t idd_scratch(const drm_walk *w, int64_t B, bool aligned) {
-    return rows_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, idd_state_floats(w), IDD_LDS_BYTES);
+    return check_sweep_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, idd_state_floats(w), IDD_LDS_BYTES);
 }
 extern "C" int64_t drm_rnea_derivatives_scratch_floats(const drm_walk *w, int64_t B) { return idd_scratch(w, B, false); }
 extern "C" int64_t drm_rnea_derivatives_scratch_floats_aligned(const drm_walk *w, int64_t B) { return idd_scratch(w, B, true); }
 
 extern "C" int drm_rnea_derivatives(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags,
                                     float *tau, float *dq, float *dqd, float *H, float *scratch, void *stream) {
-    int rc = rows_check_walk(w);
+    int rc = args_rnea_derivatives(w, q, qd, qdd, B, tau, dq, dqd, H);
     if (rc) return rc;
-    if (!q || !qd || !qdd) return fail(DRM_ERR_INVALID, "q / qd / qdd must not be NULL");
-    if (!tau && !dq && !dqd && !H) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;

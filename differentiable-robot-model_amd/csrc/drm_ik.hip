@@ -20,6 +20,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_ik.hpp"
 #include "drm_sample.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -229,19 +230,10 @@ extern "C" int drm_inverse_kinematics(const drm_walk *w, const float *q0, const 
                                       int32_t max_iters, float damping, float step, float tol_pos, float tol_rot, const float *lower,
                                       const float *upper, int32_t flags, float *q, float *err, int32_t *iters, float *scratch,
                                       void *stream) {
-    int rc = check_walk(w);
+    int rc = args_inverse_kinematics(w, q0, target_pos, target_quat, B, max_iters, damping, step, tol_pos, tol_rot, lower, upper, flags, q, err);
     if (rc) return rc;
-    const bool pos_only = (flags & DRM_IK_POSITION_ONLY) != 0;
-    if (!q0 || !target_pos || !q || !err) return fail(DRM_ERR_INVALID, "q0 / target_pos / q / err must not be NULL");
-    if ((target_quat == nullptr) != pos_only) return fail(DRM_ERR_INVALID, "target_quat must be NULL iff DRM_IK_POSITION_ONLY");
-    if ((lower == nullptr) != (upper == nullptr)) return fail(DRM_ERR_INVALID, "lower and upper must be given together");
-    if (max_iters < 0) return fail(DRM_ERR_INVALID, "max_iters must be >= 0");
-    if (!(damping > 0.0f) || !isfinite(damping) || !(step > 0.0f) || !isfinite(step))
-        return fail(DRM_ERR_INVALID, "damping and step must be finite and positive");
-    if (!(tol_pos >= 0.0f) || !isfinite(tol_pos) || !(tol_rot >= 0.0f) || !isfinite(tol_rot))
-        return fail(DRM_ERR_INVALID, "tolerances must be finite and >= 0");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
+    const bool pos_only = (flags & DRM_IK_POSITION_ONLY) != 0;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;
     const IkOpts o = {damping * damping, step, tol_pos, tol_rot};

@@ -25,6 +25,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_lagrangian.hpp"
 #include "drm_rows.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -165,18 +166,15 @@ static void launch_lagrangian_arm(const drm_walk *w, const float *q, const float
 using namespace drm;
 
 static int64_t lagrangian_scratch(const drm_walk *w, int64_t B, bool aligned) {
-    return rows_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, lagrangian_state_floats(w), LAG_LDS_BYTES);
+    return check_sweep_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, lagrangian_state_floats(w), LAG_LDS_BYTES);
 }
 extern "C" int64_t drm_lagrangian_dynamics_scratch_floats(const drm_walk *w, int64_t B) { return lagrangian_scratch(w, B, false); }
 extern "C" int64_t drm_lagrangian_dynamics_scratch_floats_aligned(const drm_walk *w, int64_t B) { return lagrangian_scratch(w, B, true); }
 
 extern "C" int drm_lagrangian_dynamics(const drm_walk *w, const float *q, const float *qd, int64_t B, int32_t flags, float *H, float *C,
                                        float *g, float *scratch, void *stream) {
-    int rc = rows_check_walk(w);
+    int rc = args_sweep_q_qd(w, q, qd, B, H || C || g);
     if (rc) return rc;
-    if (!q || !qd) return fail(DRM_ERR_INVALID, "q / qd must not be NULL");
-    if (!H && !C && !g) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;

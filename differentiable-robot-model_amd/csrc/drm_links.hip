@@ -31,6 +31,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_links.hpp"
 #include "drm_rows.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -379,15 +380,6 @@ static inline bool links_fused(const drm_walk *w, int T, int64_t B, int flags, b
     return !(flags & DRM_LINKS_COMPOSED) && (w->shape & DRM_WALK_TARGETS_ORDERED) && w->n_ops == 8 && T == 8 && rows_fused(w, B, aligned);
 }
 
-static int links_check(const drm_walk *w, const float *q, int64_t B, int T) {
-    int rc = rows_check_walk(w);
-    if (rc) return rc;
-    if (!q) return fail(DRM_ERR_INVALID, "q must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (T < 1 || T > w->n_ops) return fail(DRM_ERR_INVALID, "n_targets is not the walk's number of output slots");
-    return DRM_OK;
-}
-
 } // namespace drm
 
 using namespace drm;
@@ -396,7 +388,7 @@ using namespace drm;
 // query does not see, and the plan's scratch grows with the rows, so this covers the tail of a fused call too.  (The walks the fused
 // kernels take keep their state in LDS: 0 either way.)
 static int64_t links_scratch(const drm_walk *w, int64_t B, int state_floats) {
-    return (rows_check_walk(w) || B <= 0) ? 0 : rows_plan(B, state_floats, LINKS_LDS_BYTES).scratch_floats;
+    return (check_sweep_walk(w) || B <= 0) ? 0 : rows_plan(B, state_floats, LINKS_LDS_BYTES).scratch_floats;
 }
 extern "C" int64_t drm_link_motion_scratch_floats(const drm_walk *w, int64_t B) { return links_scratch(w, B, w ? motion_state_floats(w) : 0); }
 extern "C" int64_t drm_link_motion_scratch_floats_aligned(const drm_walk *w, int64_t B) { return drm_link_motion_scratch_floats(w, B); }
@@ -410,9 +402,8 @@ extern "C" int64_t drm_link_power_dq_scratch_floats_aligned(const drm_walk *w, i
 extern "C" int drm_link_motion(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t n_targets,
                                int32_t flags, float *pos, float *lin_vel, float *ang_vel, float *lin_acc, float *ang_acc, float *scratch,
                                void *stream) {
-    int rc = links_check(w, q, B, n_targets);
+    int rc = args_link_motion(w, q, B, n_targets, pos, lin_vel, ang_vel, lin_acc, ang_acc);
     if (rc) return rc;
-    if (!pos && !lin_vel && !ang_vel && !lin_acc && !ang_acc) return fail(DRM_ERR_INVALID, "every output is NULL");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs, T = n_targets;
@@ -449,10 +440,8 @@ extern "C" int drm_link_motion(const drm_walk *w, const float *q, const float *q
 
 extern "C" int drm_external_torques(const drm_walk *w, const float *q, const float *force, const float *torque, int64_t B,
                                     int32_t n_targets, int32_t flags, float *tau, float *scratch, void *stream) {
-    int rc = links_check(w, q, B, n_targets);
+    int rc = args_external_torques(w, q, force, torque, B, n_targets, tau);
     if (rc) return rc;
-    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
-    if (!tau) return fail(DRM_ERR_INVALID, "tau must not be NULL");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs, T = n_targets;
@@ -475,11 +464,8 @@ extern "C" int drm_external_torques(const drm_walk *w, const float *q, const flo
 
 extern "C" int drm_link_power_dq(const drm_walk *w, const float *q, const float *qd, const float *force, const float *torque, int64_t B,
                                  int32_t n_targets, int32_t flags, float *dq, float *tau, float *scratch, void *stream) {
-    int rc = links_check(w, q, B, n_targets);
+    int rc = args_link_power_dq(w, q, qd, force, torque, B, n_targets, dq);
     if (rc) return rc;
-    if (!qd) return fail(DRM_ERR_INVALID, "qd must not be NULL");
-    if (!force && !torque) return fail(DRM_ERR_INVALID, "force and torque are both NULL");
-    if (!dq) return fail(DRM_ERR_INVALID, "dq must not be NULL");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs, T = n_targets;

@@ -22,6 +22,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_osc.hpp"
 #include "drm_sample.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -299,16 +300,8 @@ static void launch_osc_arm(const drm_walk *tree, const drm_walk *chain, const fl
 extern "C" int drm_operational_space(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, int64_t B, int32_t flags,
                                      float reg, float *inertia, float *jbar, float *bias_acc, float *bias_force, float *scratch,
                                      void *stream) {
-    int rc = check_walk(tree);
+    int rc = args_operational_space(tree, chain, q, qd, B, reg, inertia, jbar, bias_acc, bias_force);
     if (rc) return rc;
-    rc = check_walk(chain);
-    if (rc) return rc;
-    if (tree->n_dofs != chain->n_dofs) return fail(DRM_ERR_INVALID, "the two walks belong to different robots");
-    if (!inertia && !jbar && !bias_acc && !bias_force) return fail(DRM_ERR_INVALID, "every output is NULL");
-    if (!q || (!qd && (bias_acc || bias_force)))
-        return fail(DRM_ERR_INVALID, "q must not be NULL, nor qd when bias_acc / bias_force are asked for");
-    if (!(reg >= 0.0f) || !isfinite(reg)) return fail(DRM_ERR_INVALID, "reg must be finite and >= 0");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = tree->n_dofs, m = (flags & DRM_OSC_POSITION_ONLY) ? 3 : 6;

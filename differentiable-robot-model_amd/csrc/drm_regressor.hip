@@ -29,6 +29,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_regressor.hpp"
 #include "drm_rows.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -158,33 +159,21 @@ __global__ void __launch_bounds__(WAVE)
     }
 }
 
-static int regressor_check_walk(const drm_walk *w) {
-    int rc = rows_check_walk(w);
-    if (rc) return rc;
-    // the largest table: a row of Y is addressed with 32-bit offsets inside the kernels
-    if ((int64_t)w->n_dofs * (REG_COLS * (int64_t)w->n_ops + w->n_dofs) >= (1 << 24))
-        return fail(DRM_ERR_UNSUPPORTED, "a row of the regressor of this walk has 2^24 entries or more (%s%ld ops, %ld DoFs)", "", (long)w->n_ops,
-                    (long)w->n_dofs);
-    return DRM_OK;
-}
-
 } // namespace drm
 
 using namespace drm;
 
 // (DRM_REGRESSOR_COMPOSED sends an arm's rows through the general kernel: its state fits LDS, no scratch either way)
 static int64_t regressor_scratch(const drm_walk *w, int64_t B, bool aligned) {
-    return regressor_check_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, regressor_state_floats(w), REG_LDS_BYTES);
+    return check_regressor_walk(w) ? 0 : rows_scratch_floats(w, B, aligned, regressor_state_floats(w), REG_LDS_BYTES);
 }
 extern "C" int64_t drm_rnea_regressor_scratch_floats(const drm_walk *w, int64_t B) { return regressor_scratch(w, B, false); }
 extern "C" int64_t drm_rnea_regressor_scratch_floats_aligned(const drm_walk *w, int64_t B) { return regressor_scratch(w, B, true); }
 
 extern "C" int drm_rnea_regressor(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, float *Y,
                                   float *scratch, void *stream) {
-    int rc = regressor_check_walk(w);
+    int rc = args_rnea_regressor(w, q, qd, B, Y);
     if (rc) return rc;
-    if (!q || !qd || !Y) return fail(DRM_ERR_INVALID, "q / qd / Y must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n = w->n_dofs;

@@ -10,6 +10,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -210,10 +211,8 @@ extern "C" int64_t drm_rnea_scratch_floats_aligned(const drm_walk *w, int64_t B)
 
 extern "C" int drm_rnea(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags,
                         float *tau, float *scratch, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_rnea(w, q, qd, B, tau);
     if (rc) return rc;
-    if (!q || !qd || !tau) return fail(DRM_ERR_INVALID, "q / qd / tau must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     const int n = w->n_dofs;
     const uint32_t align = al16(q, AL_Q) | al16(qd, AL_QD) | al16(qdd, AL_QDD) | al16(tau, AL_TAU);
@@ -291,19 +290,6 @@ extern "C" int drm_rnea(const drm_walk *w, const float *q, const float *qd, cons
     return launched();
 }
 
-// The argument checks drm_fk_rnea and drm_fk_rnea_put share (B == 0 is the caller's to answer).
-static int fk_rnea_check(const drm_walk *tree, const drm_walk *chain, const float *q, const float *qd, const float *tau, const float *pos,
-                         const float *quat, int64_t B) {
-    int rc = check_walk(tree);
-    if (rc) return rc;
-    rc = check_walk(chain);
-    if (rc) return rc;
-    if (!q || !qd || !tau || !pos || !quat) return fail(DRM_ERR_INVALID, "q / qd / tau / pos / quat must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if (tree->n_dofs != chain->n_dofs) return fail(DRM_ERR_INVALID, "the two walks belong to different robots");
-    return DRM_OK;
-}
-
 // The fused arm kernels (FK of the last link + inverse dynamics in one pass) apply to the full tiles of this call:
 // a serial 7-DoF arm whose last link is the target.  Two shapes: the tree walk IS the chain (target_op its last op: `same`), or
 // the tree walk holds the moving joints only (the host folded the fixed tail into the last of them).  Either way the
@@ -319,8 +305,9 @@ static bool fk_rnea_arm_applies(const drm_walk *tree, const drm_walk *chain, int
 extern "C" int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t target_op, const float *q, const float *qd,
                            const float *qdd, int64_t B, int32_t flags, float *tau, float *pos, float *quat, float *scratch,
                            void *stream) {
-    int rc = fk_rnea_check(tree, chain, q, qd, tau, pos, quat, B);
-    if (rc || B == 0) return rc;
+    int rc = args_fk_rnea(tree, chain, q, qd, B, tau, pos, quat);
+    if (rc) return rc;
+    if (B == 0) return DRM_OK;
 #ifndef DRM_NO_ARM_KERNEL
     const int n = tree->n_dofs;
     hipStream_t s = (hipStream_t)stream;
@@ -362,11 +349,10 @@ extern "C" int drm_fk_rnea(const drm_walk *tree, const drm_walk *chain, int32_t 
 extern "C" int drm_fk_rnea_put(const drm_walk *tree, const drm_walk *chain, int32_t target_op, const float *q, const float *qd,
                                const float *qdd, int64_t B, int32_t flags, float *tau, float *pos, float *quat, float *scratch,
                                const drm_put *put, void *stream) {
+    int rc = args_fk_rnea_put(tree, chain, q, qd, B, tau, pos, quat, put);
+    if (rc) return rc;
+    if (B == 0) return DRM_OK;
     if (!put || put->n_peers == 0) return drm_fk_rnea(tree, chain, target_op, q, qd, qdd, B, flags, tau, pos, quat, scratch, stream);
-    if (put->n_peers < 0 || put->n_peers > DRM_MAX_PEERS || put->row_offset < 0)
-        return fail(DRM_ERR_INVALID, "drm_put: n_peers must be 0 .. DRM_MAX_PEERS and row_offset >= 0");
-    int rc = fk_rnea_check(tree, chain, q, qd, tau, pos, quat, B);
-    if (rc || B == 0) return rc;
     const int n = tree->n_dofs;
     hipStream_t s = (hipStream_t)stream;
     int64_t done = 0;

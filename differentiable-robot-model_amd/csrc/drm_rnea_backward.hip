@@ -19,6 +19,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_sample.hpp"
 #include "drm_tree_dev.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 
@@ -683,18 +684,9 @@ static int rnea_backward_fan(const RneaBackwardCall &c, bool &taken) {
 extern "C" int drm_rnea_backward(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B,
                                  int32_t flags, const float *grad_tau, uint64_t param_mask, float *grad_q, float *grad_qd,
                                  float *grad_qdd, float *grad_ops_f, float *scratch, void *stream) {
-    int rc = check_walk(w);
+    int rc = args_rnea_backward(w, q, qd, B, grad_tau, param_mask, grad_q, grad_qd, grad_qdd, grad_ops_f);
     if (rc) return rc;
-    if (!q || !qd || !grad_tau) return fail(DRM_ERR_INVALID, "q / qd / grad_tau must not be NULL");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
-    if ((param_mask != 0) != (grad_ops_f != nullptr))
-        return fail(DRM_ERR_INVALID, "grad_ops_f must be given exactly when param_mask selects ops");
-    const bool want_q = grad_q != nullptr;
-    if (want_q != (grad_qd != nullptr) || want_q != (grad_qdd != nullptr))
-        return fail(DRM_ERR_INVALID, "grad_q, grad_qd and grad_qdd are produced together: give all three or none");
-    if (!want_q && !grad_ops_f) return fail(DRM_ERR_INVALID, "nothing to compute");
     if (!scratch) return fail(DRM_ERR_INVALID, "scratch must not be NULL (drm_rnea_backward_scratch_floats)");
-    if (w->capacity < 64 && (param_mask >> w->capacity)) return fail(DRM_ERR_INVALID, "param_mask selects ops beyond the walk's capacity");
     const int cap = w->capacity, n_leaves = DRM_WALK_LEAVES(w->shape);
     if (w->n_ops > 0 && (n_leaves < 1 || n_leaves > w->n_ops || n_leaves > 64))
         return fail(DRM_ERR_INVALID, "walk without its leaf count (drm_walk.shape bits 16..23; host built for an older ABI?)");

@@ -21,6 +21,7 @@
 #include "drm_dispatch.hpp"
 #include "drm_rollout.hpp"
 #include "drm_sample.hpp"
+#include "drm_args.hpp"
 
 namespace drm {
 // 7-DoF arms with their own two-samples-per-lane forward-dynamics kernel attached take the composed steps from this many 128-row
@@ -320,12 +321,8 @@ extern "C" int64_t drm_forward_dynamics_rollout_scratch_floats_aligned(const drm
 extern "C" int drm_forward_dynamics_rollout(const drm_walk *w, const float *q0, const float *qd0, const float *tau, int64_t B, int32_t T,
                                             float dt, int32_t flags, float *q_traj, float *qd_traj, float *qdd_traj, float *scratch,
                                             void *stream) {
-    int rc = check_walk(w);
+    int rc = args_forward_dynamics_rollout(w, q0, qd0, tau, B, T, dt, q_traj, qd_traj);
     if (rc) return rc;
-    if (!q0 || !qd0 || !tau || !q_traj || !qd_traj) return fail(DRM_ERR_INVALID, "q0 / qd0 / tau / q_traj / qd_traj must not be NULL");
-    if (T < 1) return fail(DRM_ERR_INVALID, "a rollout takes at least one step (T = %s%ld)", "", (long)T);
-    if (!(dt > 0.0f) || !isfinite(dt)) return fail(DRM_ERR_INVALID, "dt must be finite and positive");
-    if (B < 0) return fail(DRM_ERR_INVALID, "negative batch");
     if (B == 0) return DRM_OK;
     hipStream_t s = (hipStream_t)stream;
     const bool aligned = aligned16(q0, qd0, tau, q_traj, qd_traj, qdd_traj);

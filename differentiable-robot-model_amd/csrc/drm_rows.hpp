@@ -76,14 +76,6 @@ static inline RowsPlan rows_plan(int64_t rows, int state_floats, int lds_limit) 
     return p;
 }
 
-// check_walk, and the walk has something to sweep
-static inline int rows_check_walk(const drm_walk *w) {
-    int rc = check_walk(w);
-    if (rc) return rc;
-    if (w->n_ops < 1) return fail(DRM_ERR_INVALID, "the walk has no ops");
-    return DRM_OK;
-}
-
 // the fused single-tile kernels of these entry points take the full tiles of a 7-DoF arm whose pointers are 16-byte aligned
 static inline bool rows_fused(const drm_walk *w, int64_t B, bool aligned) {
     return arm7_walk(w) && aligned && table_aligned(w) && full_tiles_fit(B);
