@@ -116,31 +116,72 @@ class NativeLibraryError(RuntimeError):
 _libs = {}      # "hip" / "cpu" -> the loaded library
 _lock = threading.Lock()
 
-EXPORTS = ("drm_abi_version", "drm_walk_sizeof", "drm_last_error", "drm_fk", "drm_fk_jacobian", "drm_rnea", "drm_fk_backward",
-           "drm_fk_backward_scratch_floats", "drm_crba", "drm_rnea_backward",
-           "drm_rnea_backward_scratch_floats", "drm_forward_dynamics", "drm_link_rows",
-           "drm_link_rows_backward", "drm_fk_fanout", "drm_fk_fanout_links", "drm_fk_links", "drm_fk_jacobian_backward", "drm_walk_table",
-           "drm_walk_table_backward", "drm_fk_rnea", "drm_forward_dynamics_scratch_floats", "drm_crba_scratch_floats",
-           "drm_rnea_scratch_floats", "drm_fk_mse", "drm_fk_mse_scratch_floats", "drm_rnea_scratch_floats_aligned",
-           "drm_crba_scratch_floats_aligned", "drm_forward_dynamics_scratch_floats_aligned", "drm_special_load", "drm_fk_rnea_put",
-           "drm_fk_mse_links", "drm_walk_table_links", "drm_walk_table_links_backward", "drm_forward_dynamics_rollout",
-           "drm_forward_dynamics_rollout_scratch_floats", "drm_forward_dynamics_rollout_scratch_floats_aligned",
-           "drm_inverse_kinematics", "drm_inverse_kinematics_scratch_floats", "drm_inverse_kinematics_scratch_floats_aligned",
-           "drm_operational_space", "drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned",
-           "drm_forward_dynamics_derivatives", "drm_forward_dynamics_derivatives_scratch_floats",
-           "drm_forward_dynamics_derivatives_scratch_floats_aligned",
-           "drm_rnea_regressor", "drm_rnea_regressor_scratch_floats", "drm_rnea_regressor_scratch_floats_aligned",
-           "drm_lagrangian_dynamics", "drm_lagrangian_dynamics_scratch_floats", "drm_lagrangian_dynamics_scratch_floats_aligned",
-           "drm_rnea_derivatives", "drm_rnea_derivatives_scratch_floats", "drm_rnea_derivatives_scratch_floats_aligned",
-           "drm_energy", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
-           "drm_link_motion", "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
-           "drm_external_torques", "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
-           "drm_link_power_dq", "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
-           "drm_contact_torques", "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
-           "drm_contact_torques_vjp", "drm_contact_torques_vjp_scratch_floats", "drm_contact_torques_vjp_scratch_floats_aligned",
-           "drm_contact_rollout", "drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned",
-           "drm_collision_cost", "drm_collision_cost_scratch_floats", "drm_collision_cost_scratch_floats_aligned",
-           "drm_sphere_distances", "drm_sphere_distances_scratch_floats", "drm_sphere_distances_scratch_floats_aligned")
+vp, i32, i64, u64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+P = ctypes.POINTER
+wp = P(DrmWalk)
+_CONTACT = [P(DrmContactPlane), vp, P(DrmJointSprings), vp, vp]              # plane, radius, springs, lower, upper
+_COLLISION = [P(DrmCollisionSpheres), P(DrmCollisionWorld), P(DrmCollisionPairs)]
+_LINK_TABLE = [P(DrmLinkPieces), P(DrmLinkForms), i32, vp, vp, vp, i32, vp, vp]
+
+# name -> (restype, argtypes) of every entry point of include/drm_hip.h, in the header's argument order (tests/test_host_logic.py
+# holds this table to the header): load_library declares from it.  A new entry point is one row here and one wrapper below.
+PROTOTYPES = {
+    "drm_abi_version": (ctypes.c_int, []),
+    "drm_walk_sizeof": (ctypes.c_int, []),
+    "drm_last_error": (ctypes.c_char_p, []),
+    "drm_special_load": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, P(vp)]),
+    "drm_fk": (ctypes.c_int, [wp, vp, i64, i32, vp, vp, vp]),
+    "drm_fk_links": (ctypes.c_int, [wp, vp, i64, i32, vp, vp, vp]),
+    "drm_fk_fanout": (ctypes.c_int, [wp, i32, vp, i64, vp, vp, vp]),
+    "drm_fk_fanout_links": (ctypes.c_int, [wp, i32, vp, i64, vp, vp, vp]),
+    "drm_fk_jacobian": (ctypes.c_int, [wp, vp, i64, vp, vp, vp, vp, vp]),
+    "drm_rnea": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    "drm_crba": (ctypes.c_int, [wp, vp, i64, vp, vp, vp]),
+    "drm_forward_dynamics": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    "drm_fk_rnea": (ctypes.c_int, [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "drm_fk_rnea_put": (ctypes.c_int, [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, P(DrmPut), vp]),
+    "drm_fk_backward": (ctypes.c_int, [wp, vp, i64, i32, vp, vp, u64, vp, vp, vp, vp]),
+    "drm_fk_jacobian_backward": (ctypes.c_int, [wp, vp, i64, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
+    "drm_fk_backward_scratch_floats": (i64, [i64, i32]),
+    "drm_rnea_backward": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, vp, u64, vp, vp, vp, vp, vp, vp]),
+    "drm_rnea_backward_scratch_floats": (i64, [i64, i32, i32, i32]),
+    "drm_fk_mse": (ctypes.c_int, [wp, vp, vp, i64, u64, vp, vp, vp, vp, vp]),
+    "drm_fk_mse_links": (ctypes.c_int, [wp, vp, vp, P(DrmLinkPieces), i32, vp, vp, i64, u64, vp, vp, vp, vp, vp]),
+    "drm_fk_mse_scratch_floats": (i64, [i64, i32]),
+    "drm_link_rows": (ctypes.c_int, [vp, i32, vp, vp]),
+    "drm_link_rows_backward": (ctypes.c_int, [vp, vp, i32, vp, vp]),
+    "drm_walk_table": (ctypes.c_int, [vp, i32, vp, vp, vp, i32, vp, vp]),
+    "drm_walk_table_backward": (ctypes.c_int, [vp, i32, vp, vp, vp, i32, vp, vp]),
+    "drm_walk_table_links": (ctypes.c_int, _LINK_TABLE),
+    "drm_walk_table_links_backward": (ctypes.c_int, _LINK_TABLE),
+    "drm_forward_dynamics_rollout": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, f32, i32, vp, vp, vp, vp, vp]),
+    "drm_inverse_kinematics": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "drm_operational_space": (ctypes.c_int, [wp, wp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]),
+    "drm_forward_dynamics_derivatives": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    "drm_rnea_regressor": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    "drm_lagrangian_dynamics": (ctypes.c_int, [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "drm_rnea_derivatives": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    "drm_energy": (ctypes.c_int, [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "drm_link_motion": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "drm_external_torques": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp]),
+    "drm_link_power_dq": (ctypes.c_int, [wp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+    "drm_contact_torques": (ctypes.c_int, [wp, vp, vp, i64, i32] + _CONTACT + [i32, vp, vp, vp, vp, vp]),
+    "drm_contact_torques_vjp": (ctypes.c_int, [wp, vp, vp, vp, i64, i32] + _CONTACT + [i32, vp, vp, vp, vp]),
+    "drm_contact_rollout": (ctypes.c_int, [wp, wp, vp, vp, vp, i64, i32, f32, i32, i32] + _CONTACT + [vp, vp, vp, vp, vp]),
+    "drm_collision_cost": (ctypes.c_int, [wp, vp, i64, i32] + _COLLISION + [P(DrmCollisionParams), i32, vp, vp, vp, vp]),
+    "drm_sphere_distances": (ctypes.c_int, [wp, vp, i64, i32] + _COLLISION + [i32, vp, vp, vp, vp, vp]),
+}
+# the scratch queries: (walks..., B, what the query takes after B); ``_aligned`` is for callers whose pointers are 16-byte aligned
+for _base in ("drm_rnea", "drm_crba", "drm_forward_dynamics", "drm_forward_dynamics_rollout", "drm_inverse_kinematics",
+              "drm_forward_dynamics_derivatives", "drm_rnea_regressor", "drm_lagrangian_dynamics", "drm_rnea_derivatives", "drm_energy",
+              "drm_link_motion", "drm_external_torques", "drm_link_power_dq", "drm_contact_torques", "drm_contact_torques_vjp"):
+    PROTOTYPES[_base + "_scratch_floats"] = PROTOTYPES[_base + "_scratch_floats_aligned"] = (i64, [wp, i64])
+for _base in ("drm_operational_space", "drm_contact_rollout"):
+    PROTOTYPES[_base + "_scratch_floats"] = PROTOTYPES[_base + "_scratch_floats_aligned"] = (i64, [wp, wp, i64])
+for _base in ("drm_collision_cost", "drm_sphere_distances"):
+    PROTOTYPES[_base + "_scratch_floats"] = (i64, [wp, i64, i32])
+    PROTOTYPES[_base + "_scratch_floats_aligned"] = (i64, [wp, i64, i32, i32, i32, i32])
+EXPORTS = tuple(PROTOTYPES)
 
 
 def library_for(device):
@@ -178,129 +219,9 @@ def load_library(path: str = None, kind: str = "cuda"):
             lib = ctypes.CDLL(path)
         except OSError as err:
             raise NativeLibraryError("cannot load %s: %s" % (path, err))
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        wp = ctypes.POINTER(DrmWalk)
-        lib.drm_abi_version.restype = ctypes.c_int
-        lib.drm_abi_version.argtypes = []
-        lib.drm_last_error.restype = ctypes.c_char_p
-        lib.drm_last_error.argtypes = []
-        lib.drm_fk.restype = ctypes.c_int
-        lib.drm_fk.argtypes = [wp, vp, i64, i32, vp, vp, vp]
-        lib.drm_fk_links.restype = ctypes.c_int
-        lib.drm_fk_links.argtypes = [wp, vp, i64, i32, vp, vp, vp]
-        lib.drm_fk_fanout.restype = ctypes.c_int
-        lib.drm_fk_fanout.argtypes = [wp, i32, vp, i64, vp, vp, vp]
-        lib.drm_fk_fanout_links.restype = ctypes.c_int
-        lib.drm_fk_fanout_links.argtypes = [wp, i32, vp, i64, vp, vp, vp]
-        lib.drm_fk_jacobian.restype = ctypes.c_int
-        lib.drm_fk_jacobian.argtypes = [wp, vp, i64, vp, vp, vp, vp, vp]
-        lib.drm_rnea.restype = ctypes.c_int
-        lib.drm_rnea.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp]
-        lib.drm_rnea_scratch_floats.restype = i64
-        lib.drm_rnea_scratch_floats.argtypes = [wp, i64]
-        lib.drm_fk_backward.restype = ctypes.c_int
-        lib.drm_fk_backward.argtypes = [wp, vp, i64, i32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp]
-        lib.drm_fk_jacobian_backward.restype = ctypes.c_int
-        lib.drm_fk_jacobian_backward.argtypes = [wp, vp, i64, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp]
-        lib.drm_fk_backward_scratch_floats.restype = i64
-        lib.drm_fk_backward_scratch_floats.argtypes = [i64, i32]
-        lib.drm_rnea_backward.restype = ctypes.c_int
-        lib.drm_rnea_backward.argtypes = [wp, vp, vp, vp, i64, i32, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, vp]
-        lib.drm_rnea_backward_scratch_floats.restype = i64
-        lib.drm_rnea_backward_scratch_floats.argtypes = [i64, i32, i32, i32]
-        lib.drm_link_rows.restype = ctypes.c_int
-        lib.drm_link_rows.argtypes = [vp, i32, vp, vp]
-        lib.drm_link_rows_backward.restype = ctypes.c_int
-        lib.drm_link_rows_backward.argtypes = [vp, vp, i32, vp, vp]
-        lib.drm_walk_table.restype = ctypes.c_int
-        lib.drm_walk_table.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
-        lib.drm_walk_table_backward.restype = ctypes.c_int
-        lib.drm_walk_table_backward.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
-        lib.drm_forward_dynamics.restype = ctypes.c_int
-        lib.drm_forward_dynamics.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp]
-        lib.drm_forward_dynamics_scratch_floats.restype = i64
-        lib.drm_forward_dynamics_scratch_floats.argtypes = [wp, i64]
-        lib.drm_crba.restype = ctypes.c_int
-        lib.drm_crba.argtypes = [wp, vp, i64, vp, vp, vp]
-        lib.drm_crba_scratch_floats.restype = i64
-        lib.drm_crba_scratch_floats.argtypes = [wp, i64]
-        lib.drm_fk_rnea.restype = ctypes.c_int
-        lib.drm_fk_rnea.argtypes = [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
-        lib.drm_fk_rnea_put.restype = ctypes.c_int
-        lib.drm_fk_rnea_put.argtypes = [wp, wp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.POINTER(DrmPut), vp]
-        lib.drm_forward_dynamics_rollout.restype = ctypes.c_int
-        lib.drm_forward_dynamics_rollout.argtypes = [wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, vp, vp, vp, vp, vp]
-        f32 = ctypes.c_float
-        lib.drm_inverse_kinematics.restype = ctypes.c_int
-        lib.drm_inverse_kinematics.argtypes = [wp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp, vp, i32, vp, vp, vp, vp, vp]
-        for name in ("drm_rnea_scratch_floats_aligned", "drm_crba_scratch_floats_aligned",
-                     "drm_forward_dynamics_scratch_floats_aligned", "drm_forward_dynamics_rollout_scratch_floats",
-                     "drm_forward_dynamics_rollout_scratch_floats_aligned", "drm_inverse_kinematics_scratch_floats",
-                     "drm_inverse_kinematics_scratch_floats_aligned", "drm_forward_dynamics_derivatives_scratch_floats",
-                     "drm_forward_dynamics_derivatives_scratch_floats_aligned", "drm_rnea_regressor_scratch_floats",
-                     "drm_rnea_regressor_scratch_floats_aligned", "drm_lagrangian_dynamics_scratch_floats",
-                     "drm_lagrangian_dynamics_scratch_floats_aligned", "drm_rnea_derivatives_scratch_floats",
-                     "drm_rnea_derivatives_scratch_floats_aligned", "drm_energy_scratch_floats", "drm_energy_scratch_floats_aligned",
-                     "drm_link_motion_scratch_floats", "drm_link_motion_scratch_floats_aligned",
-                     "drm_external_torques_scratch_floats", "drm_external_torques_scratch_floats_aligned",
-                     "drm_link_power_dq_scratch_floats", "drm_link_power_dq_scratch_floats_aligned",
-                     "drm_contact_torques_scratch_floats", "drm_contact_torques_scratch_floats_aligned",
-                     "drm_contact_torques_vjp_scratch_floats", "drm_contact_torques_vjp_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64]
-        for name in ("drm_contact_rollout_scratch_floats", "drm_contact_rollout_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, wp, i64]
-        pp, sp = ctypes.POINTER(DrmContactPlane), ctypes.POINTER(DrmJointSprings)
-        lib.drm_contact_torques.restype = ctypes.c_int
-        lib.drm_contact_torques.argtypes = [wp, vp, vp, i64, i32, pp, vp, sp, vp, vp, i32, vp, vp, vp, vp, vp]
-        lib.drm_contact_torques_vjp.restype = ctypes.c_int
-        lib.drm_contact_torques_vjp.argtypes = [wp, vp, vp, vp, i64, i32, pp, vp, sp, vp, vp, i32, vp, vp, vp, vp]
-        lib.drm_contact_rollout.restype = ctypes.c_int
-        lib.drm_contact_rollout.argtypes = [wp, wp, vp, vp, vp, i64, i32, ctypes.c_float, i32, i32, pp, vp, sp, vp, vp, vp, vp, vp, vp, vp]
-        for name in ("drm_collision_cost_scratch_floats", "drm_sphere_distances_scratch_floats"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, i64, i32]
-            getattr(lib, name + "_aligned").restype = i64
-            getattr(lib, name + "_aligned").argtypes = [wp, i64, i32, i32, i32, i32]
-        csp, cwp, cpp = ctypes.POINTER(DrmCollisionSpheres), ctypes.POINTER(DrmCollisionWorld), ctypes.POINTER(DrmCollisionPairs)
-        lib.drm_collision_cost.restype = ctypes.c_int
-        lib.drm_collision_cost.argtypes = [wp, vp, i64, i32, csp, cwp, cpp, ctypes.POINTER(DrmCollisionParams), i32, vp, vp, vp, vp]
-        lib.drm_sphere_distances.restype = ctypes.c_int
-        lib.drm_sphere_distances.argtypes = [wp, vp, i64, i32, csp, cwp, cpp, i32, vp, vp, vp, vp, vp]
-        lib.drm_operational_space.restype = ctypes.c_int
-        lib.drm_operational_space.argtypes = [wp, wp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]
-        for name in ("drm_operational_space_scratch_floats", "drm_operational_space_scratch_floats_aligned"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [wp, wp, i64]
-        lib.drm_forward_dynamics_derivatives.restype = ctypes.c_int
-        lib.drm_forward_dynamics_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-        lib.drm_rnea_regressor.restype = ctypes.c_int
-        lib.drm_rnea_regressor.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp]
-        lib.drm_lagrangian_dynamics.restype = ctypes.c_int
-        lib.drm_lagrangian_dynamics.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
-        lib.drm_rnea_derivatives.restype = ctypes.c_int
-        lib.drm_rnea_derivatives.argtypes = [wp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-        lib.drm_energy.restype = ctypes.c_int
-        lib.drm_energy.argtypes = [wp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
-        lib.drm_link_motion.restype = ctypes.c_int
-        lib.drm_link_motion.argtypes = [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-        lib.drm_external_torques.restype = ctypes.c_int
-        lib.drm_external_torques.argtypes = [wp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
-        lib.drm_link_power_dq.restype = ctypes.c_int
-        lib.drm_link_power_dq.argtypes = [wp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]
-        lib.drm_special_load.restype = ctypes.c_int
-        lib.drm_special_load.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
-        lib.drm_fk_mse.restype = ctypes.c_int
-        lib.drm_fk_mse.argtypes = [wp, vp, vp, i64, ctypes.c_uint64, vp, vp, vp, vp, vp]
-        lib.drm_walk_table_links.restype = ctypes.c_int
-        lib.drm_walk_table_links.argtypes = [ctypes.POINTER(DrmLinkPieces), ctypes.POINTER(DrmLinkForms), i32, vp, vp, vp, i32, vp, vp]
-        lib.drm_walk_table_links_backward.restype = ctypes.c_int
-        lib.drm_walk_table_links_backward.argtypes = [ctypes.POINTER(DrmLinkPieces), ctypes.POINTER(DrmLinkForms), i32, vp, vp, vp, i32, vp, vp]
-        lib.drm_fk_mse_links.restype = ctypes.c_int
-        lib.drm_fk_mse_links.argtypes = [wp, vp, vp, ctypes.POINTER(DrmLinkPieces), i32, vp, vp, i64, ctypes.c_uint64, vp, vp, vp, vp, vp]
-        lib.drm_fk_mse_scratch_floats.restype = i64
-        lib.drm_fk_mse_scratch_floats.argtypes = [i64, i32]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.drm_abi_version() != ABI_VERSION:
             raise NativeLibraryError("ABI version mismatch: library %d, binding %d" % (lib.drm_abi_version(), ABI_VERSION))
         if lib.drm_walk_sizeof() != ctypes.sizeof(DrmWalk):
@@ -539,6 +460,98 @@ def _contiguous_strides(shape):
     return tuple(reversed(st))
 
 
+# ------------------------------------------------------------------ the pieces of a wrapper
+# Every wrapper below reads top to bottom: inputs (_dev_f32, _same_batch), outputs (_outputs / _wanted / torch.empty), flags,
+# scratch (_scratch), and the one C call (_launch) with its arguments in the header's order.  The five eager wrappers that are timed
+# per call (those with a hostcall prologue: fk, fk_jacobian, rnea, crba, forward_dynamics) spell the same steps out instead: measured
+# on the host build at B = 1, _same_batch, _scratch, _launch and _ptr each cost them 0.1 to 0.3 us of a 9 to 12 us call.
+def _ptr(t):
+    """The address of a tensor's data; NULL for None."""
+    return t.data_ptr() if t is not None else None
+
+
+def _ref(struct):
+    """A struct by reference; NULL for None."""
+    return ctypes.byref(struct) if struct is not None else None
+
+
+def _rnea_flags(gravity, damping) -> int:
+    return (RNEA_GRAVITY if gravity else 0) | (RNEA_DAMPING if damping else 0)
+
+
+def _composed(flag, name: str) -> bool:
+    """An entry point's ``composed`` argument, or DRM_<name>_COMPOSED=1 in the environment (tests, A/B)."""
+    return bool(flag) or os.environ.get("DRM_%s_COMPOSED" % name) == "1"
+
+
+def _launch(lib, fn, device, *args):
+    """The one C call of a wrapper: on `device`, the caller's current stream appended to `args`, the return code checked."""
+    with _on_device(device):
+        _check(fn(*args, _stream(device)), lib)
+
+
+def _same_batch(message: str, first, second, third=None) -> int:
+    """The batch size of `first`; ValueError(message) when `second` or `third` (None: absent) has another."""
+    B = first.shape[0]
+    if (second is not None and second.shape[0] != B) or (third is not None and third.shape[0] != B):
+        raise ValueError(message)
+    return B
+
+
+def _scratch(lib, base: str, walks, B: int, composed: bool, device, extra=()):
+    """The scratch of entry point ``base`` over B rows of ``walks`` (None: not needed): the walks as the call takes them, by
+    reference (_ref; None where the entry point takes NULL).  The callers' tensors come from _dev_f32 / _plan_input / _outputs /
+    torch.empty, 16-byte aligned, so the ``_aligned`` query sizes the call; ``composed`` (the entry point's DRM_*_COMPOSED flag) takes
+    the composed path / general kernel on every row: the size for any pointers.  ``extra``: what the query takes after B."""
+    query = getattr(lib, base + ("_scratch_floats" if composed else "_scratch_floats_aligned"))
+    need = query(*walks, B, *extra)
+    return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
+
+
+def _wanted(want, names, shapes, device):
+    """The ``want=`` protocol: `want` must name at least one of `names`; the named outputs (`shapes`: one per name) are views of one
+    allocation, and the result lists them in the order of `names`, None for the others."""
+    want = tuple(want)
+    if not want or any(w not in names for w in want):
+        raise ValueError("want must name at least one of %s" % (names,))
+    made = dict(zip(want, _outputs(device, *[shapes[names.index(w)] for w in want])))
+    return tuple(made.get(name) for name in names)
+
+
+def _wrench(t, name: str, B: int, n_targets: int):
+    """A [B, T, 3] force or torque array as the [B, 3 T] rows the kernels take (None stays None: zero)."""
+    if t is None:
+        return None
+    if t.ndim != 3 or tuple(t.shape) != (B, n_targets, 3):
+        raise ValueError("%s must be [%d, %d, 3], got %s" % (name, B, n_targets, tuple(t.shape)))
+    return _dev_f32(t.reshape(B, n_targets * 3), name, n_targets * 3)
+
+
+def _rollout_args(q0, qd0, tau, dt: float, n_dofs: int):
+    """(q0, qd0, T, B) of a rollout from (q0, qd0) [B, n] under tau [T, B, n] with step dt, checked."""
+    q0, qd0 = _dev_f32(q0, "q0", n_dofs), _dev_f32(qd0, "qd0", n_dofs)
+    if not isinstance(tau, torch.Tensor) or tau.ndim != 3 or tau.shape[2] != n_dofs:
+        raise ValueError("tau must be [T, B, %d], got %s" % (n_dofs, tuple(getattr(tau, "shape", ()))))
+    T, B = int(tau.shape[0]), int(q0.shape[0])
+    if qd0.shape[0] != B or tau.shape[1] != B:
+        raise ValueError("q0 / qd0 / tau batch sizes differ")
+    if T < 1:
+        raise ValueError("a rollout takes at least one step (tau has T = %d)" % T)
+    if not (math.isfinite(dt) and dt > 0):
+        raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+    return q0, qd0, T, B
+
+
+def _grad_ops(lib, query: str, sizes, prog: WalkProgram, ops_f, device, param_mask: int, wanted):
+    """(grad_ops_f [capacity, 32] or None when `param_mask` selects no op, scratch of the entry point's fixed-size query
+    `lib.<query>(*sizes)`) of a backward call.  `wanted`: the call has something else to compute; with neither there is nothing to
+    launch: (None, None), and the library is not asked."""
+    grad_ops = torch.empty(prog.capacity, ops_f.shape[1], device=device, dtype=torch.float32) if param_mask else None
+    if grad_ops is None and not wanted:
+        return None, None
+    return grad_ops, torch.empty(max(1, getattr(lib, query)(*sizes)), device=device, dtype=torch.float32)
+
+
 def fk(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs: int, squeeze: bool = False):
     """pos [B, T, 3], quat [B, T, 4] of the walk's targets ([B, 3], [B, 4] for one target with ``squeeze``: the same
     memory without the T axis, so the single-link API returns it without a slicing op)."""
@@ -560,10 +573,9 @@ def fk(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs: int, squeeze:
         pos, quat = _outputs(q.device, (B, n_targets, 3), (B, n_targets, 4))
     if B == 0:
         return pos, quat
-    walk = _walk_struct(prog, ops_f, ops_i, n_dofs)
+    walk = ctypes.byref(_walk_struct(prog, ops_f, ops_i, n_dofs))
     with _on_device(q.device):
-        _check(lib.drm_fk(ctypes.byref(walk), q.data_ptr(), B, n_targets, pos.data_ptr(), quat.data_ptr(),
-                          _stream(q.device)), lib)
+        _check(lib.drm_fk(walk, q.data_ptr(), B, n_targets, pos.data_ptr(), quat.data_ptr(), _stream(q.device)), lib)
     return pos, quat
 
 
@@ -577,10 +589,8 @@ def fk_links(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs: int):
     quat = torch.empty(n_targets, B, 4, device=q.device, dtype=torch.float32)
     if B == 0:
         return pos, quat
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    with _on_device(q.device):
-        _check(lib.drm_fk_links(ctypes.byref(walk), q.data_ptr(), B, n_targets, pos.data_ptr(), quat.data_ptr(),
-                                _stream(q.device)), lib)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    _launch(lib, lib.drm_fk_links, q.device, walk, _ptr(q), B, n_targets, _ptr(pos), _ptr(quat))
     return pos, quat
 
 
@@ -607,9 +617,7 @@ def fk_fanout(chains, q, n_dofs: int, link_major: bool = False, own=None):
         if len(cache) > 64:
             cache.clear()
         cache[key] = walks
-    with _on_device(q.device):
-        _check((lib.drm_fk_fanout_links if link_major else lib.drm_fk_fanout)(
-            walks, T, q.data_ptr(), B, pos.data_ptr(), quat.data_ptr(), _stream(q.device)), lib)
+    _launch(lib, lib.drm_fk_fanout_links if link_major else lib.drm_fk_fanout, q.device, walks, T, _ptr(q), B, _ptr(pos), _ptr(quat))
     return pos, quat
 
 
@@ -629,10 +637,10 @@ def fk_jacobian(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):
     pos, quat, lin, ang = _outputs(q.device, (B, 3), (B, 4), (B, 3, n_dofs), (B, 3, n_dofs))
     if B == 0:
         return pos, quat, lin, ang
-    walk = _walk_struct(prog, ops_f, ops_i, n_dofs)
+    walk = ctypes.byref(_walk_struct(prog, ops_f, ops_i, n_dofs))
     with _on_device(q.device):
-        _check(lib.drm_fk_jacobian(ctypes.byref(walk), q.data_ptr(), B, pos.data_ptr(), quat.data_ptr(),
-                                   lin.data_ptr(), ang.data_ptr(), _stream(q.device)), lib)
+        _check(lib.drm_fk_jacobian(walk, q.data_ptr(), B, pos.data_ptr(), quat.data_ptr(), lin.data_ptr(), ang.data_ptr(),
+                                   _stream(q.device)), lib)
     return pos, quat, lin, ang
 
 
@@ -641,7 +649,7 @@ def rnea(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity: bool, use
     fast = hostcall()
     if fast is not None and isinstance(qd, torch.Tensor) and (qdd is None or isinstance(qdd, torch.Tensor)):
         walk = _walk_struct(prog, ops_f, ops_i, n_dofs)
-        flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
+        flags = _rnea_flags(include_gravity, use_damping)
         with _on_device(q.device):
             tau, rc = fast.rnea(_fn_addr(lib, "drm_rnea"), _fn_addr(lib, "drm_rnea_scratch_floats_aligned"), ctypes.addressof(walk), q, qd,
                                 qdd, n_dofs, flags, _stream_int(q.device))
@@ -658,29 +666,15 @@ def rnea(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity: bool, use
     tau = torch.empty(B, n_dofs, device=q.device, dtype=torch.float32)
     if B == 0:
         return tau
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
-    walk = _walk_struct(prog, ops_f, ops_i, n_dofs)
-    scratch = _rnea_scratch(lib, walk, B, q.device)
+    flags = _rnea_flags(include_gravity, use_damping)
+    walk = ctypes.byref(_walk_struct(prog, ops_f, ops_i, n_dofs))
+    # the body forces that robots with a long segment keep between the two sweeps (_dev_f32 guarantees aligned pointers)
+    need = lib.drm_rnea_scratch_floats_aligned(walk, B)
+    scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
     with _on_device(q.device):
-        _check(lib.drm_rnea(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(),
-                            qdd.data_ptr() if qdd is not None else None, B, flags, tau.data_ptr(),
+        _check(lib.drm_rnea(walk, q.data_ptr(), qd.data_ptr(), qdd.data_ptr() if qdd is not None else None, B, flags, tau.data_ptr(),
                             scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return tau
-
-
-def _rnea_scratch(lib, walk, B, device):
-    """The body forces robots with a long segment keep between the two sweeps of drm_rnea (None: not needed)."""
-    need = int(lib.drm_rnea_scratch_floats_aligned(ctypes.byref(walk), B))    # (_dev_f32 / _plan_input guarantee aligned pointers)
-    return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
-
-
-def _scratch(lib, base: str, walks, B: int, composed: bool, device, extra=()):
-    """The scratch of entry point ``base`` over B rows of ``walks`` (None: not needed).  The callers' tensors come from _dev_f32 /
-    _outputs / torch.empty, 16-byte aligned, so the ``_aligned`` query sizes the call; ``composed`` (the entry point's DRM_*_COMPOSED
-    flag) takes the composed path / general kernel on every row: the size for any pointers.  ``extra``: what the query takes after B."""
-    query = getattr(lib, base + ("_scratch_floats" if composed else "_scratch_floats_aligned"))
-    need = int(query(*[ctypes.byref(w) for w in walks], B, *extra))
-    return torch.empty(need, device=device, dtype=torch.float32) if need > 0 else None
 
 
 def rnea_backward(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, grad_tau, include_gravity: bool, use_damping: bool,
@@ -695,19 +689,15 @@ def rnea_backward(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, grad_tau, include
     grad_tau = _dev_f32(grad_tau, "grad_tau", n_dofs)
     B, dev = q.shape[0], q.device
     gin = tuple(torch.empty(B, n_dofs, device=dev, dtype=torch.float32) for _ in range(3)) if want_grad_inputs else None
-    grad_ops = torch.empty(prog.capacity, ops_f.shape[1], device=dev, dtype=torch.float32) if param_mask else None
-    if gin is None and grad_ops is None:
+    grad_ops, scratch = _grad_ops(lib, "drm_rnea_backward_scratch_floats", (B, prog.capacity, n_dofs, prog.n_slots), prog, ops_f, dev,
+                                  param_mask, want_grad_inputs)
+    if scratch is None:
         return None, None
-    scratch = torch.empty(max(1, lib.drm_rnea_backward_scratch_floats(B, prog.capacity, n_dofs, prog.n_slots)),
-                          device=dev, dtype=torch.float32)
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(dev):
-        _check(lib.drm_rnea_backward(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), ptr(qdd), B, flags,
-                                     grad_tau.data_ptr(), ctypes.c_uint64(param_mask),
-                                     ptr(gin[0]) if gin else None, ptr(gin[1]) if gin else None,
-                                     ptr(gin[2]) if gin else None, ptr(grad_ops), scratch.data_ptr(), _stream(dev)), lib)
+    flags = _rnea_flags(include_gravity, use_damping)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    gq, gqd, gqdd = gin or (None, None, None)
+    _launch(lib, lib.drm_rnea_backward, dev, walk, _ptr(q), _ptr(qd), _ptr(qdd), B, flags, _ptr(grad_tau), param_mask,
+            _ptr(gq), _ptr(gqd), _ptr(gqdd), _ptr(grad_ops), _ptr(scratch))
     return gin, grad_ops
 
 
@@ -744,8 +734,7 @@ class LinkRows(torch.autograd.Function):
         lib = library_for(params.device)
         params = params.contiguous().to(torch.float32)
         rows = torch.empty(params.shape[0], 32, device=params.device, dtype=torch.float32)
-        with _on_device(params.device):
-            _check(lib.drm_link_rows(params.data_ptr(), params.shape[0], rows.data_ptr(), _stream(params.device)), lib)
+        _launch(lib, lib.drm_link_rows, params.device, _ptr(params), params.shape[0], _ptr(rows))
         ctx.save_for_backward(params)
         return rows
 
@@ -759,9 +748,7 @@ class LinkRows(torch.autograd.Function):
         lib = library_for(params.device)
         grad_rows = grad_rows.contiguous().to(torch.float32)
         grad = torch.empty_like(params)
-        with _on_device(params.device):
-            _check(lib.drm_link_rows_backward(params.data_ptr(), grad_rows.data_ptr(), params.shape[0], grad.data_ptr(),
-                                              _stream(params.device)), lib)
+        _launch(lib, lib.drm_link_rows_backward, params.device, _ptr(params), _ptr(grad_rows), params.shape[0], _ptr(grad))
         return grad
 
 
@@ -779,9 +766,7 @@ class WalkTable(torch.autograd.Function):
         params = torch.cat([p.reshape(-1).to(device=dev, dtype=torch.float32) for p in pieces])
         assert params.numel() == n_links * 20, "20 floats per learnable link"
         ops_f = torch.empty_like(base)
-        with _on_device(dev):
-            _check(lib.drm_walk_table(params.data_ptr(), n_links, base.data_ptr(), sel.data_ptr(), gsign.data_ptr(),
-                                      base.numel(), ops_f.data_ptr(), _stream(dev)), lib)
+        _launch(lib, lib.drm_walk_table, dev, _ptr(params), n_links, _ptr(base), _ptr(sel), _ptr(gsign), base.numel(), _ptr(ops_f))
         ctx.save_for_backward(params, sel, gsign, base, *pieces)
         ctx.n_links, ctx.shapes = n_links, [tuple(p.shape) for p in pieces]
         return ops_f
@@ -809,9 +794,8 @@ class WalkTable(torch.autograd.Function):
         lib = library_for(params.device)
         g = grad_ops_f.contiguous().to(torch.float32)
         grad = torch.empty_like(params)
-        with _on_device(params.device):
-            _check(lib.drm_walk_table_backward(params.data_ptr(), ctx.n_links, g.data_ptr(), sel.data_ptr(), gsign.data_ptr(),
-                                               g.numel(), grad.data_ptr(), _stream(params.device)), lib)
+        _launch(lib, lib.drm_walk_table_backward, params.device, _ptr(params), ctx.n_links, _ptr(g), _ptr(sel), _ptr(gsign), g.numel(),
+                _ptr(grad))
         out, off = [], 0
         for i, shape in enumerate(ctx.shapes):
             n = 1
@@ -897,9 +881,8 @@ class WalkTableLinks(torch.autograd.Function):
                 held.append(t)
             plan.checked = tuple([t.data_ptr() for t in sources]) if as_given and dev == plan.device else None
         ops_f = torch.empty_like(base)
-        with _on_device(dev):
-            _check(lib.drm_walk_table_links(plan.pieces(held), plan.forms, plan.n_links, base.data_ptr(), sel.data_ptr(), gsign.data_ptr(),
-                                            base.numel(), ops_f.data_ptr(), _stream(dev)), lib)
+        _launch(lib, lib.drm_walk_table_links, dev, plan.pieces(held), plan.forms, plan.n_links, _ptr(base), _ptr(sel), _ptr(gsign),
+                base.numel(), _ptr(ops_f))
         ctx.save_for_backward(sel, gsign, base, *sources)
         ctx.plan = plan
         return ops_f
@@ -929,9 +912,8 @@ class WalkTableLinks(torch.autograd.Function):
                                       t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in sources]
         g = grad_ops_f.contiguous().to(torch.float32)
         grad = torch.empty(plan.n_links * 20, device=dev, dtype=torch.float32)
-        with _on_device(dev):
-            _check(lib.drm_walk_table_links_backward(plan.pieces(held), plan.forms, plan.n_links, g.data_ptr(), sel.data_ptr(),
-                                                     gsign.data_ptr(), g.numel(), grad.data_ptr(), _stream(dev)), lib)
+        _launch(lib, lib.drm_walk_table_links_backward, dev, plan.pieces(held), plan.forms, plan.n_links, _ptr(g), _ptr(sel), _ptr(gsign),
+                g.numel(), _ptr(grad))
         out = []
         needs = ctx.needs_input_grad
         for k, (i, t, size) in enumerate(zip(plan.live, sources, plan.sizes)):
@@ -950,7 +932,7 @@ def forward_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, f, include_gravity:
     fast = hostcall()
     if fast is not None and isinstance(qd, torch.Tensor) and isinstance(f, torch.Tensor):
         walk = _walk_struct(prog, ops_f, ops_i, n_dofs)      # (reads the table's address only)
-        flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
+        flags = _rnea_flags(include_gravity, use_damping)
         with _on_device(q.device):
             qdd, rc = fast.forward_dynamics(_fn_addr(lib, "drm_forward_dynamics"), _fn_addr(lib, "drm_forward_dynamics_scratch_floats_aligned"),
                                             ctypes.addressof(walk), q, qd, f, n_dofs, flags, _stream_int(q.device))
@@ -965,15 +947,14 @@ def forward_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, f, include_gravity:
     qdd = torch.empty(B, n_dofs, device=q.device, dtype=torch.float32)
     if B == 0:
         return qdd
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    flags = _rnea_flags(include_gravity, use_damping)
+    walk = ctypes.byref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     # the per-link records of the articulated-body sweeps, when the launch keeps them in HBM
-    need = int(lib.drm_forward_dynamics_scratch_floats_aligned(ctypes.byref(walk), B))
+    need = lib.drm_forward_dynamics_scratch_floats_aligned(walk, B)
     scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
     with _on_device(q.device):
-        _check(lib.drm_forward_dynamics(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), f.data_ptr(), B, flags,
-                                        qdd.data_ptr(), scratch.data_ptr() if scratch is not None else None,
-                                        _stream(q.device)), lib)
+        _check(lib.drm_forward_dynamics(walk, q.data_ptr(), qd.data_ptr(), f.data_ptr(), B, flags, qdd.data_ptr(),
+                                        scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return qdd
 
 
@@ -982,31 +963,16 @@ def forward_dynamics_rollout(prog: WalkProgram, ops_f, ops_i, q0, qd0, tau, dt: 
     """(q_traj, qd_traj, qdd_traj or None), each [T, B, n]: T steps of forward dynamics and an Euler integrator from (q0, qd0) [B, n]
     under the joint torques tau [T, B, n] (time-major; include/drm_hip.h drm_forward_dynamics_rollout)."""
     lib = _lib_of(q0, "q0", ops_f)
-    q0, qd0 = _dev_f32(q0, "q0", n_dofs), _dev_f32(qd0, "qd0", n_dofs)
-    if not isinstance(tau, torch.Tensor) or tau.ndim != 3 or tau.shape[2] != n_dofs:
-        raise ValueError("tau must be [T, B, %d], got %s" % (n_dofs, tuple(getattr(tau, "shape", ()))))
-    T, B = int(tau.shape[0]), int(q0.shape[0])
-    if qd0.shape[0] != B or tau.shape[1] != B:
-        raise ValueError("q0 / qd0 / tau batch sizes differ")
-    if T < 1:
-        raise ValueError("a rollout takes at least one step (tau has T = %d)" % T)
-    if not (math.isfinite(dt) and dt > 0):
-        raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+    q0, qd0, T, B = _rollout_args(q0, qd0, tau, dt, n_dofs)
     tau = _dev_f32(tau.reshape(T * B, n_dofs), "tau", n_dofs)
-    outs = _outputs(q0.device, *(((T, B, n_dofs),) * (3 if want_qdd else 2)))
-    q_traj, qd_traj = outs[0], outs[1]
-    qdd_traj = outs[2] if want_qdd else None
+    q_traj, qd_traj, qdd_traj = (_outputs(q0.device, *[(T, B, n_dofs)] * (3 if want_qdd else 2)) + [None])[:3]
     if B == 0:
         return q_traj, qd_traj, qdd_traj
-    flags = (RNEA_GRAVITY if gravity else 0) | (RNEA_DAMPING if damping else 0) | (ROLLOUT_EXPLICIT_EULER if explicit else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    need = int(lib.drm_forward_dynamics_rollout_scratch_floats_aligned(ctypes.byref(walk), B))    # (_dev_f32 / _outputs: aligned)
-    scratch = torch.empty(need, device=q0.device, dtype=torch.float32) if need > 0 else None
-    with _on_device(q0.device):
-        _check(lib.drm_forward_dynamics_rollout(ctypes.byref(walk), q0.data_ptr(), qd0.data_ptr(), tau.data_ptr(), B, T, float(dt), flags,
-                                                q_traj.data_ptr(), qd_traj.data_ptr(),
-                                                qdd_traj.data_ptr() if qdd_traj is not None else None,
-                                                scratch.data_ptr() if scratch is not None else None, _stream(q0.device)), lib)
+    flags = _rnea_flags(gravity, damping) | (ROLLOUT_EXPLICIT_EULER if explicit else 0)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    scratch = _scratch(lib, "drm_forward_dynamics_rollout", (walk,), B, False, q0.device)
+    _launch(lib, lib.drm_forward_dynamics_rollout, q0.device, walk, _ptr(q0), _ptr(qd0), _ptr(tau), B, T, float(dt), flags,
+            _ptr(q_traj), _ptr(qd_traj), _ptr(qdd_traj), _ptr(scratch))
     return q_traj, qd_traj, qdd_traj
 
 
@@ -1020,9 +986,7 @@ def inverse_kinematics(prog: WalkProgram, ops_f, ops_i, q0, target_pos, target_q
     q0 = _dev_f32(q0, "q0", n_dofs)
     target_pos = _dev_f32(target_pos, "target_pos", 3)
     target_quat = _dev_f32(target_quat, "target_quat", 4) if target_quat is not None else None
-    B = int(q0.shape[0])
-    if target_pos.shape[0] != B or (target_quat is not None and target_quat.shape[0] != B):
-        raise ValueError("q0 / target_pos / target_quat batch sizes differ")
+    B = _same_batch("q0 / target_pos / target_quat batch sizes differ", q0, target_pos, target_quat)
     if (lower is None) != (upper is None):
         raise ValueError("lower and upper must be given together")
     if lower is not None:
@@ -1033,16 +997,11 @@ def inverse_kinematics(prog: WalkProgram, ops_f, ops_i, q0, target_pos, target_q
     if B == 0:
         return q, err, iters
     flags = (IK_POSITION_ONLY if target_quat is None else 0) | (IK_COMPOSED if composed else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_inverse_kinematics", (walk,), B, composed, q0.device)
-    with _on_device(q0.device):
-        _check(lib.drm_inverse_kinematics(ctypes.byref(walk), q0.data_ptr(), target_pos.data_ptr(),
-                                          target_quat.data_ptr() if target_quat is not None else None, B, int(max_iters),
-                                          float(damping), float(step), float(tol_pos), float(tol_rot),
-                                          lower.data_ptr() if lower is not None else None,
-                                          upper.data_ptr() if upper is not None else None, flags, q.data_ptr(), err.data_ptr(),
-                                          iters.data_ptr(), scratch.data_ptr() if scratch is not None else None,
-                                          _stream(q0.device)), lib)
+    _launch(lib, lib.drm_inverse_kinematics, q0.device, walk, _ptr(q0), _ptr(target_pos), _ptr(target_quat), B, int(max_iters),
+            float(damping), float(step), float(tol_pos), float(tol_rot), _ptr(lower), _ptr(upper), flags, _ptr(q), _ptr(err), _ptr(iters),
+            _ptr(scratch))
     return q, err, iters
 
 
@@ -1054,22 +1013,17 @@ def operational_space(tree, chain, q, qd, include_gravity: bool, use_damping: bo
     (DRM_OSC_COMPOSED: tests, A/B)."""
     lib = _lib_of(q, "q", tree[1])
     q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B:
-        raise ValueError("q / qd batch sizes differ")
+    B = _same_batch("q / qd batch sizes differ", q, qd)
     m = 3 if position_only else 6
     inertia, jbar, bias_acc, bias_force = _outputs(q.device, (B, m, m), (B, n_dofs, m), (B, m), (B, m))
     if B == 0:
         return inertia, jbar, bias_acc, bias_force
-    flags = ((RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) |
-             (OSC_POSITION_ONLY if position_only else 0) | (OSC_COMPOSED if composed else 0))
-    wt = _walk_struct(tree[0], tree[1].detach(), tree[2], n_dofs)
-    wc = _walk_struct(chain[0], chain[1].detach(), chain[2], n_dofs)
+    flags = _rnea_flags(include_gravity, use_damping) | (OSC_POSITION_ONLY if position_only else 0) | (OSC_COMPOSED if composed else 0)
+    wt = _ref(_walk_struct(tree[0], tree[1].detach(), tree[2], n_dofs))
+    wc = _ref(_walk_struct(chain[0], chain[1].detach(), chain[2], n_dofs))
     scratch = _scratch(lib, "drm_operational_space", (wt, wc), B, composed, q.device)
-    with _on_device(q.device):
-        _check(lib.drm_operational_space(ctypes.byref(wt), ctypes.byref(wc), q.data_ptr(), qd.data_ptr(), B, flags, float(reg),
-                                         inertia.data_ptr(), jbar.data_ptr(), bias_acc.data_ptr(), bias_force.data_ptr(),
-                                         scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    _launch(lib, lib.drm_operational_space, q.device, wt, wc, _ptr(q), _ptr(qd), B, flags, float(reg), _ptr(inertia),
+            _ptr(jbar), _ptr(bias_acc), _ptr(bias_force), _ptr(scratch))
     return inertia, jbar, bias_acc, bias_force
 
 
@@ -1082,20 +1036,16 @@ def forward_dynamics_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, f, incl
     if not prog.slots_unique:
         raise RuntimeError("backward RNEA needs a walk whose branch points own their save slots")
     q, qd, f = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(f, "f", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B or f.shape[0] != B:
-        raise ValueError("q / qd / f batch sizes differ")
+    B = _same_batch("q / qd / f batch sizes differ", q, qd, f)
     qdd, dq, dqd, minv = _outputs(q.device, (B, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs))
     if B == 0:
         return qdd, dq, dqd, minv
-    composed = bool(composed) or os.environ.get("DRM_FDD_COMPOSED") == "1"
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (FDD_COMPOSED if composed else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "FDD")
+    flags = _rnea_flags(include_gravity, use_damping) | (FDD_COMPOSED if composed else 0)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_forward_dynamics_derivatives", (walk,), B, composed, q.device)
-    with _on_device(q.device):
-        _check(lib.drm_forward_dynamics_derivatives(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), f.data_ptr(), B, flags,
-                                                    qdd.data_ptr(), dq.data_ptr(), dqd.data_ptr(), minv.data_ptr(),
-                                                    scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    _launch(lib, lib.drm_forward_dynamics_derivatives, q.device, walk, _ptr(q), _ptr(qd), _ptr(f), B, flags, _ptr(qdd), _ptr(dq),
+            _ptr(dqd), _ptr(minv), _ptr(scratch))
     return qdd, dq, dqd, minv
 
 
@@ -1105,19 +1055,15 @@ def rnea_regressor(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity:
     drm_rnea_regressor).  ``composed`` forces the general kernel on every row (DRM_REGRESSOR_COMPOSED: tests, A/B)."""
     lib = _lib_of(q, "q", ops_f)
     q, qd, qdd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(qdd, "qdd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B or qdd.shape[0] != B:
-        raise ValueError("q / qd / qdd batch sizes differ")
+    B = _same_batch("q / qd / qdd batch sizes differ", q, qd, qdd)
     P = REGRESSOR_COLS * prog.n_ops + (n_dofs if use_damping else 0)
     (Y,) = _outputs(q.device, (B, n_dofs, P))
     if B == 0:
         return Y
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (REGRESSOR_COMPOSED if composed else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    flags = _rnea_flags(include_gravity, use_damping) | (REGRESSOR_COMPOSED if composed else 0)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_rnea_regressor", (walk,), B, composed, q.device)
-    with _on_device(q.device):
-        _check(lib.drm_rnea_regressor(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, Y.data_ptr(),
-                                      scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    _launch(lib, lib.drm_rnea_regressor, q.device, walk, _ptr(q), _ptr(qd), _ptr(qdd), B, flags, _ptr(Y), _ptr(scratch))
     return Y
 
 
@@ -1127,9 +1073,7 @@ def lagrangian_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, cor
     ``composed`` (or DRM_LAGRANGIAN_COMPOSED=1 in the environment) forces the general kernel on every row (tests, A/B)."""
     lib = _lib_of(q, "q", ops_f)
     q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B:
-        raise ValueError("q / qd batch sizes differ")
+    B = _same_batch("q / qd batch sizes differ", q, qd)
     if coriolis_only:
         H, g = None, None
         (C,) = _outputs(q.device, (B, n_dofs, n_dofs))
@@ -1137,14 +1081,11 @@ def lagrangian_dynamics(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, cor
         H, C, g = _outputs(q.device, (B, n_dofs, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs))
     if B == 0:
         return H, C, g
-    composed = bool(composed) or os.environ.get("DRM_LAGRANGIAN_COMPOSED") == "1"
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "LAGRANGIAN")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_lagrangian_dynamics", (walk,), B, composed, q.device)
-    with _on_device(q.device):
-        _check(lib.drm_lagrangian_dynamics(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, LAGRANGIAN_COMPOSED if composed else 0,
-                                           H.data_ptr() if H is not None else None, C.data_ptr(),
-                                           g.data_ptr() if g is not None else None,
-                                           scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    _launch(lib, lib.drm_lagrangian_dynamics, q.device, walk, _ptr(q), _ptr(qd), B, LAGRANGIAN_COMPOSED if composed else 0, _ptr(H),
+            _ptr(C), _ptr(g), _ptr(scratch))
     return H, C, g
 
 
@@ -1155,20 +1096,16 @@ def rnea_derivatives(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravit
     environment) forces the general kernel on every row (tests, A/B)."""
     lib = _lib_of(q, "q", ops_f)
     q, qd, qdd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(qdd, "qdd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B or qdd.shape[0] != B:
-        raise ValueError("q / qd / qdd batch sizes differ")
+    B = _same_batch("q / qd / qdd batch sizes differ", q, qd, qdd)
     tau, dq, dqd, H = _outputs(q.device, (B, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs), (B, n_dofs, n_dofs))
     if B == 0:
         return tau, dq, dqd, H
-    composed = bool(composed) or os.environ.get("DRM_IDD_COMPOSED") == "1"
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0) | (IDD_COMPOSED if composed else 0)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "IDD")
+    flags = _rnea_flags(include_gravity, use_damping) | (IDD_COMPOSED if composed else 0)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_rnea_derivatives", (walk,), B, composed, q.device)
-    with _on_device(q.device):
-        _check(lib.drm_rnea_derivatives(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), B, flags, tau.data_ptr(),
-                                        dq.data_ptr(), dqd.data_ptr(), H.data_ptr(),
-                                        scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+    _launch(lib, lib.drm_rnea_derivatives, q.device, walk, _ptr(q), _ptr(qd), _ptr(qdd), B, flags, _ptr(tau), _ptr(dq), _ptr(dqd),
+            _ptr(H), _ptr(scratch))
     return tau, dq, dqd, H
 
 
@@ -1182,32 +1119,20 @@ def energy(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, want=ENERGY_OUTP
     environment) forces the general kernel on every row (tests, A/B)."""
     lib = _lib_of(q, "q", ops_f)
     q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B:
-        raise ValueError("q / qd batch sizes differ")
-    want = tuple(want)
-    if not want or any(w not in ENERGY_OUTPUTS for w in want):
-        raise ValueError("want must name at least one of %s" % (ENERGY_OUTPUTS,))
-    shapes = {"kinetic": (B,), "potential": (B,), "momentum": (B, n_dofs), "dkinetic_dq": (B, n_dofs), "gravity": (B, n_dofs)}
-    made = dict(zip(want, _outputs(q.device, *[shapes[w] for w in want])))
-    outs = tuple(made.get(name) for name in ENERGY_OUTPUTS)
+    B = _same_batch("q / qd batch sizes differ", q, qd)
+    outs = _wanted(want, ENERGY_OUTPUTS, [(B,), (B,), (B, n_dofs), (B, n_dofs), (B, n_dofs)], q.device)
     if B == 0:
         return outs
-    composed = bool(composed) or os.environ.get("DRM_ENERGY_COMPOSED") == "1"
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "ENERGY")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_energy", (walk,), B, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_energy(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, ENERGY_COMPOSED if composed else 0,
-                              *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
+    kinetic, potential, momentum, dkinetic_dq, gravity = outs
+    _launch(lib, lib.drm_energy, q.device, walk, _ptr(q), _ptr(qd), B, ENERGY_COMPOSED if composed else 0, _ptr(kinetic),
+            _ptr(potential), _ptr(momentum), _ptr(dkinetic_dq), _ptr(gravity), _ptr(scratch))
     return outs
 
 
 LINK_MOTION_OUTPUTS = ("position", "linear_velocity", "angular_velocity", "linear_acceleration", "angular_acceleration")
-
-
-def _links_composed(composed) -> bool:
-    return bool(composed) or os.environ.get("DRM_LINKS_COMPOSED") == "1"
 
 
 def link_motion(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, n_targets: int, n_dofs: int, want=LINK_MOTION_OUTPUTS, composed: bool = False):
@@ -1219,23 +1144,16 @@ def link_motion(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, n_targets: int, n_d
     q = _dev_f32(q, "q", n_dofs)
     qd = _dev_f32(qd, "qd", n_dofs) if qd is not None else None
     qdd = _dev_f32(qdd, "qdd", n_dofs) if qdd is not None else None
-    B = int(q.shape[0])
-    if any(t is not None and t.shape[0] != B for t in (qd, qdd)):
-        raise ValueError("q / qd / qdd batch sizes differ")
-    want = tuple(want)
-    if not want or any(w not in LINK_MOTION_OUTPUTS for w in want):
-        raise ValueError("want must name at least one of %s" % (LINK_MOTION_OUTPUTS,))
-    made = dict(zip(want, _outputs(q.device, *[(B, n_targets, 3)] * len(want))))
-    outs = tuple(made.get(name) for name in LINK_MOTION_OUTPUTS)
+    B = _same_batch("q / qd / qdd batch sizes differ", q, qd, qdd)
+    outs = _wanted(want, LINK_MOTION_OUTPUTS, [(B, n_targets, 3)] * 5, q.device)
     if B == 0:
         return outs
-    composed = _links_composed(composed)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "LINKS")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_link_motion", (walk,), B, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_link_motion(ctypes.byref(walk), q.data_ptr(), ptr(qd), ptr(qdd), B, n_targets, LINKS_COMPOSED if composed else 0,
-                                   *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
+    pos, lin_vel, ang_vel, lin_acc, ang_acc = outs
+    _launch(lib, lib.drm_link_motion, q.device, walk, _ptr(q), _ptr(qd), _ptr(qdd), B, n_targets, LINKS_COMPOSED if composed else 0,
+            _ptr(pos), _ptr(lin_vel), _ptr(ang_vel), _ptr(lin_acc), _ptr(ang_acc), _ptr(scratch))
     return outs
 
 
@@ -1248,24 +1166,15 @@ def external_torques(prog: WalkProgram, ops_f, ops_i, q, force, torque, n_target
     B = int(q.shape[0])
     if force is None and torque is None:
         raise ValueError("force and torque are both None")
-
-    def wrench(t, name):
-        if t is None:
-            return None
-        if t.ndim != 3 or tuple(t.shape) != (B, n_targets, 3):
-            raise ValueError("%s must be [%d, %d, 3], got %s" % (name, B, n_targets, tuple(t.shape)))
-        return _dev_f32(t.reshape(B, n_targets * 3), name, n_targets * 3)
-    force, torque = wrench(force, "force"), wrench(torque, "torque")
+    force, torque = _wrench(force, "force", B, n_targets), _wrench(torque, "torque", B, n_targets)
     (tau,) = _outputs(q.device, (B, n_dofs))
     if B == 0:
         return tau
-    composed = _links_composed(composed)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "LINKS")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_external_torques", (walk,), B, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_external_torques(ctypes.byref(walk), q.data_ptr(), ptr(force), ptr(torque), B, n_targets,
-                                        LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(scratch), _stream(q.device)), lib)
+    _launch(lib, lib.drm_external_torques, q.device, walk, _ptr(q), _ptr(force), _ptr(torque), B, n_targets,
+            LINKS_COMPOSED if composed else 0, _ptr(tau), _ptr(scratch))
     return tau
 
 
@@ -1278,29 +1187,18 @@ def link_power_dq(prog: WalkProgram, ops_f, ops_i, q, qd, force, torque, n_targe
     launch.  Either of ``force`` / ``torque`` may be None (zero), not both.  ``composed``: as for link_motion."""
     lib = _lib_of(q, "q", ops_f)
     q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B:
-        raise ValueError("q / qd batch sizes differ")
+    B = _same_batch("q / qd batch sizes differ", q, qd)
     if force is None and torque is None:
         raise ValueError("force and torque are both None")
-
-    def wrench(t, name):
-        if t is None:
-            return None
-        if t.ndim != 3 or tuple(t.shape) != (B, n_targets, 3):
-            raise ValueError("%s must be [%d, %d, 3], got %s" % (name, B, n_targets, tuple(t.shape)))
-        return _dev_f32(t.reshape(B, n_targets * 3), name, n_targets * 3)
-    force, torque = wrench(force, "force"), wrench(torque, "torque")
+    force, torque = _wrench(force, "force", B, n_targets), _wrench(torque, "torque", B, n_targets)
     dq, tau = (_outputs(q.device, *[(B, n_dofs)] * (2 if want_tau else 1)) + [None])[:2]
     if B == 0:
         return dq, tau
-    composed = _links_composed(composed)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "LINKS")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_link_power_dq", (walk,), B, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_link_power_dq(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), ptr(force), ptr(torque), B, n_targets,
-                                     LINKS_COMPOSED if composed else 0, dq.data_ptr(), ptr(tau), ptr(scratch), _stream(q.device)), lib)
+    _launch(lib, lib.drm_link_power_dq, q.device, walk, _ptr(q), _ptr(qd), _ptr(force), _ptr(torque), B, n_targets,
+            LINKS_COMPOSED if composed else 0, _ptr(dq), _ptr(tau), _ptr(scratch))
     return dq, tau
 
 
@@ -1334,25 +1232,18 @@ def contact_torques(prog: WalkProgram, ops_f, ops_i, q, qd, n_targets: int, n_do
     None with ``want_wrenches`` False).  ``plane`` / ``radius`` / ``springs``: _contact_structs.  ``composed``: as for link_motion."""
     lib = _lib_of(q, "q", ops_f)
     q, qd = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B:
-        raise ValueError("q / qd batch sizes differ")
+    B = _same_batch("q / qd batch sizes differ", q, qd)
     if plane is None:
         raise ValueError("contact_torques needs a plane")
     pl, radius, sp, lower, upper = _contact_structs(plane, radius, springs, n_targets, n_dofs, q.device)
-    outs = _outputs(q.device, (B, n_dofs), *([(B, n_targets, 3)] * (2 if want_wrenches else 0)))
-    tau, force, moment = outs[0], (outs[1] if want_wrenches else None), (outs[2] if want_wrenches else None)
+    tau, force, moment = (_outputs(q.device, (B, n_dofs), *[(B, n_targets, 3)] * (2 if want_wrenches else 0)) + [None, None])[:3]
     if B == 0:
         return tau, force, moment
-    composed = _links_composed(composed)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "LINKS")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_contact_torques", (walk,), B, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_contact_torques(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), B, n_targets, ctypes.byref(pl), ptr(radius),
-                                       ctypes.byref(sp) if sp is not None else None, ptr(lower), ptr(upper),
-                                       LINKS_COMPOSED if composed else 0, tau.data_ptr(), ptr(force), ptr(moment), ptr(scratch),
-                                       _stream(q.device)), lib)
+    _launch(lib, lib.drm_contact_torques, q.device, walk, _ptr(q), _ptr(qd), B, n_targets, _ref(pl), _ptr(radius), _ref(sp),
+            _ptr(lower), _ptr(upper), LINKS_COMPOSED if composed else 0, _ptr(tau), _ptr(force), _ptr(moment), _ptr(scratch))
     return tau, force, moment
 
 
@@ -1364,28 +1255,18 @@ def contact_torques_vjp(prog: WalkProgram, ops_f, ops_i, q, qd, grad_tau, n_targ
     ``composed``: as for link_motion."""
     lib = _lib_of(q, "q", ops_f)
     q, qd, grad_tau = _dev_f32(q, "q", n_dofs), _dev_f32(qd, "qd", n_dofs), _dev_f32(grad_tau, "grad_tau", n_dofs)
-    B = int(q.shape[0])
-    if qd.shape[0] != B or grad_tau.shape[0] != B:
-        raise ValueError("q / qd / grad_tau batch sizes differ")
+    B = _same_batch("q / qd / grad_tau batch sizes differ", q, qd, grad_tau)
     if plane is None and springs is None:
         raise ValueError("contact_torques_vjp needs a plane or springs")
-    want = tuple(want)
-    if not want or any(w not in ("grad_q", "grad_qd") for w in want):
-        raise ValueError("want must name at least one of ('grad_q', 'grad_qd')")
+    grad_q, grad_qd = _wanted(want, ("grad_q", "grad_qd"), [(B, n_dofs), (B, n_dofs)], q.device)
     pl, radius, sp, lower, upper = _contact_structs(plane, radius, springs, n_targets, n_dofs, q.device)
-    made = dict(zip(want, _outputs(q.device, *[(B, n_dofs)] * len(want))))
-    grad_q, grad_qd = made.get("grad_q"), made.get("grad_qd")
     if B == 0:
         return grad_q, grad_qd
-    composed = _links_composed(composed)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    composed = _composed(composed, "LINKS")
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     scratch = _scratch(lib, "drm_contact_torques_vjp", (walk,), B, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    ref = lambda st: ctypes.byref(st) if st is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_contact_torques_vjp(ctypes.byref(walk), q.data_ptr(), qd.data_ptr(), grad_tau.data_ptr(), B, n_targets, ref(pl),
-                                           ptr(radius), ref(sp), ptr(lower), ptr(upper), LINKS_COMPOSED if composed else 0, ptr(grad_q),
-                                           ptr(grad_qd), ptr(scratch), _stream(q.device)), lib)
+    _launch(lib, lib.drm_contact_torques_vjp, q.device, walk, _ptr(q), _ptr(qd), _ptr(grad_tau), B, n_targets, _ref(pl), _ptr(radius),
+            _ref(sp), _ptr(lower), _ptr(upper), LINKS_COMPOSED if composed else 0, _ptr(grad_q), _ptr(grad_qd), _ptr(scratch))
     return grad_q, grad_qd
 
 
@@ -1398,7 +1279,7 @@ def _collision_structs(tables, device):
                         ("boxes", wb, torch.float32), ("pairs", pairs, torch.int32)):
         if t is not None and (t.device != device or t.dtype != dt or not t.is_contiguous()):
             raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, device))
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    ptr = lambda t: _ptr(t) if t is not None and t.numel() else None      # (an empty table is NULL)
     S = int(spheres.shape[0])
     sp = DrmCollisionSpheres(ptr(spheres), ptr(start), S)
     world = None
@@ -1412,9 +1293,9 @@ def _collision_scratch(lib, base: str, walk, B: int, n_targets: int, tables, com
     """_scratch of a collision entry point: the ``_aligned`` query is told the targets and the sizes of the tables, so a call
     that the fused kernel takes allocates for its B % 64 tail rows alone (nothing when there are none)."""
     if composed:
-        return _scratch(lib, base, (walk,), B, True, device, extra=(int(tables[0].shape[0]),))
+        return _scratch(lib, base, (_ref(walk),), B, True, device, extra=(int(tables[0].shape[0]),))
     count = lambda t: int(t.shape[0]) if t is not None else 0
-    return _scratch(lib, base, (walk,), B, False, device,
+    return _scratch(lib, base, (_ref(walk),), B, False, device,
                     extra=(n_targets, count(tables[0]), count(tables[2]) + count(tables[3]), count(tables[4])))
 
 
@@ -1427,23 +1308,16 @@ def collision_cost(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs: i
     lib = _lib_of(q, "q", ops_f)
     q = _dev_f32(q, "q", n_dofs)
     B = int(q.shape[0])
-    want = tuple(want)
-    if not want or any(w not in ("cost", "dq") for w in want):
-        raise ValueError("want must name at least one of ('cost', 'dq')")
+    cost, dq = _wanted(want, ("cost", "dq"), [(B,), (B, n_dofs)], q.device)
     sp, world, pr, S = _collision_structs(tables, q.device)
-    made = dict(zip(want, _outputs(q.device, *[{"cost": (B,), "dq": (B, n_dofs)}[w] for w in want])))
-    cost, dq = made.get("cost"), made.get("dq")
     if B == 0:
         return cost, dq
-    composed = _links_composed(composed)
+    composed = _composed(composed, "LINKS")
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
     scratch = _collision_scratch(lib, "drm_collision_cost", walk, B, n_targets, tables, composed, q.device)
     par = DrmCollisionParams(*[float(x) for x in params])
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    ref = lambda st: ctypes.byref(st) if st is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_collision_cost(ctypes.byref(walk), q.data_ptr(), B, n_targets, ctypes.byref(sp), ref(world), ref(pr), ctypes.byref(par),
-                                      LINKS_COMPOSED if composed else 0, ptr(cost), ptr(dq), ptr(scratch), _stream(q.device)), lib)
+    _launch(lib, lib.drm_collision_cost, q.device, _ref(walk), _ptr(q), B, n_targets, _ref(sp), _ref(world), _ref(pr), _ref(par),
+            LINKS_COMPOSED if composed else 0, _ptr(cost), _ptr(dq), _ptr(scratch))
     return cost, dq
 
 
@@ -1459,23 +1333,17 @@ def sphere_distances(prog: WalkProgram, ops_f, ops_i, q, n_targets: int, n_dofs:
     lib = _lib_of(q, "q", ops_f)
     q = _dev_f32(q, "q", n_dofs)
     B = int(q.shape[0])
-    want = tuple(want)
-    if not want or any(w not in SPHERE_DISTANCE_OUTPUTS for w in want):
-        raise ValueError("want must name at least one of %s" % (SPHERE_DISTANCE_OUTPUTS,))
+    S = int(tables[0].shape[0])
+    outs = _wanted(want, SPHERE_DISTANCE_OUTPUTS, [(B, S, 3), (B, S), (B, S)], q.device)
     sp, world, pr, S = _collision_structs(tables, q.device)
-    shapes = {"center": (B, S, 3), "world_distance": (B, S), "self_distance": (B, S)}
-    made = dict(zip(want, _outputs(q.device, *[shapes[w] for w in want])))
-    outs = tuple(made.get(name) for name in SPHERE_DISTANCE_OUTPUTS)
     if B == 0:
         return outs
-    composed = _links_composed(composed)
+    composed = _composed(composed, "LINKS")
     walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
     scratch = _collision_scratch(lib, "drm_sphere_distances", walk, B, n_targets, tables, composed, q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    ref = lambda st: ctypes.byref(st) if st is not None else None
-    with _on_device(q.device):
-        _check(lib.drm_sphere_distances(ctypes.byref(walk), q.data_ptr(), B, n_targets, ctypes.byref(sp), ref(world), ref(pr),
-                                        LINKS_COMPOSED if composed else 0, *[ptr(t) for t in outs], ptr(scratch), _stream(q.device)), lib)
+    center, world_distance, self_distance = outs
+    _launch(lib, lib.drm_sphere_distances, q.device, _ref(walk), _ptr(q), B, n_targets, _ref(sp), _ref(world), _ref(pr),
+            LINKS_COMPOSED if composed else 0, _ptr(center), _ptr(world_distance), _ptr(self_distance), _ptr(scratch))
     return outs
 
 
@@ -1486,40 +1354,21 @@ def contact_rollout(dyn, links, q0, qd0, tau, dt: float, gravity: bool, damping:
     (program, ops_f, ops_i) of the dynamics walk and of the many-target FK walk of the contact links (``links`` None without a
     plane).  ``plane`` / ``radius`` / ``springs``: _contact_structs; ``composed``: the composed steps on every row."""
     lib = _lib_of(q0, "q0", dyn[1])
-    q0, qd0 = _dev_f32(q0, "q0", n_dofs), _dev_f32(qd0, "qd0", n_dofs)
-    if not isinstance(tau, torch.Tensor) or tau.ndim != 3 or tau.shape[2] != n_dofs:
-        raise ValueError("tau must be [T, B, %d], got %s" % (n_dofs, tuple(getattr(tau, "shape", ()))))
-    T, B = int(tau.shape[0]), int(q0.shape[0])
-    if qd0.shape[0] != B or tau.shape[1] != B:
-        raise ValueError("q0 / qd0 / tau batch sizes differ")
-    if T < 1:
-        raise ValueError("a rollout takes at least one step (tau has T = %d)" % T)
-    if not (math.isfinite(dt) and dt > 0):
-        raise ValueError("dt must be finite and positive (got %r)" % (dt,))
+    q0, qd0, T, B = _rollout_args(q0, qd0, tau, dt, n_dofs)
     if plane is None and springs is None:
         raise ValueError("neither a contact plane nor joint-limit springs: compute_forward_dynamics_rollout is the plain rollout")
     tau = _dev_f32(tau.reshape(T * B, n_dofs), "tau", n_dofs)
     pl, radius, sp, lower, upper = _contact_structs(plane, radius, springs, n_targets, n_dofs, q0.device)
-    outs = _outputs(q0.device, *(((T, B, n_dofs),) * (3 if want_qdd else 2)))
-    q_traj, qd_traj = outs[0], outs[1]
-    qdd_traj = outs[2] if want_qdd else None
+    q_traj, qd_traj, qdd_traj = (_outputs(q0.device, *[(T, B, n_dofs)] * (3 if want_qdd else 2)) + [None])[:3]
     if B == 0:
         return q_traj, qd_traj, qdd_traj
-    composed = _links_composed(composed)
-    flags = ((RNEA_GRAVITY if gravity else 0) | (RNEA_DAMPING if damping else 0) | (ROLLOUT_EXPLICIT_EULER if explicit else 0) |
-             (LINKS_COMPOSED if composed else 0))
-    dwalk = _walk_struct(dyn[0], dyn[1].detach(), dyn[2], n_dofs)
-    lwalk = _walk_struct(links[0], links[1].detach(), links[2], n_dofs) if pl is not None else None
-    lref = ctypes.byref(lwalk) if lwalk is not None else None
-    query = lib.drm_contact_rollout_scratch_floats if composed else lib.drm_contact_rollout_scratch_floats_aligned
-    need = int(query(ctypes.byref(dwalk), lref, B))
-    scratch = torch.empty(need, device=q0.device, dtype=torch.float32) if need > 0 else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with _on_device(q0.device):
-        _check(lib.drm_contact_rollout(ctypes.byref(dwalk), lref, q0.data_ptr(), qd0.data_ptr(), tau.data_ptr(), B, T, float(dt), flags,
-                                       n_targets, ctypes.byref(pl) if pl is not None else None, ptr(radius),
-                                       ctypes.byref(sp) if sp is not None else None, ptr(lower), ptr(upper), q_traj.data_ptr(),
-                                       qd_traj.data_ptr(), ptr(qdd_traj), ptr(scratch), _stream(q0.device)), lib)
+    composed = _composed(composed, "LINKS")
+    flags = _rnea_flags(gravity, damping) | (ROLLOUT_EXPLICIT_EULER if explicit else 0) | (LINKS_COMPOSED if composed else 0)
+    dwalk = _ref(_walk_struct(dyn[0], dyn[1].detach(), dyn[2], n_dofs))
+    lwalk = _ref(_walk_struct(links[0], links[1].detach(), links[2], n_dofs)) if pl is not None else None
+    scratch = _scratch(lib, "drm_contact_rollout", (dwalk, lwalk), B, composed, q0.device)
+    _launch(lib, lib.drm_contact_rollout, q0.device, dwalk, lwalk, _ptr(q0), _ptr(qd0), _ptr(tau), B, T, float(dt), flags,
+            n_targets, _ref(pl), _ptr(radius), _ref(sp), _ptr(lower), _ptr(upper), _ptr(q_traj), _ptr(qd_traj), _ptr(qdd_traj), _ptr(scratch))
     return q_traj, qd_traj, qdd_traj
 
 
@@ -1541,13 +1390,12 @@ def crba(prog: WalkProgram, ops_f, ops_i, q, n_dofs: int):
     H = torch.empty(B, n_dofs, n_dofs, device=q.device, dtype=torch.float32)
     if B == 0:
         return H
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
+    walk = ctypes.byref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
     # robots with a long segment collect the lower triangle of H in scratch before its rows are written
-    need = int(lib.drm_crba_scratch_floats_aligned(ctypes.byref(walk), B))
+    need = lib.drm_crba_scratch_floats_aligned(walk, B)
     scratch = torch.empty(need, device=q.device, dtype=torch.float32) if need > 0 else None
     with _on_device(q.device):
-        _check(lib.drm_crba(ctypes.byref(walk), q.data_ptr(), B, H.data_ptr(),
-                            scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
+        _check(lib.drm_crba(walk, q.data_ptr(), B, H.data_ptr(), scratch.data_ptr() if scratch is not None else None, _stream(q.device)), lib)
     return H
 
 
@@ -1566,18 +1414,14 @@ def fk_backward(prog: WalkProgram, ops_f, ops_i, q, grad_pos, n_targets: int, n_
         grad_rot = _dev_f32(grad_rot.reshape(B, n_targets * 9), "grad_rot", n_targets * 9)
     dev = q.device
     grad_q = torch.empty(B, n_dofs, device=dev, dtype=torch.float32) if want_grad_q else None
-    grad_ops = torch.empty(prog.capacity, ops_f.shape[1], device=dev, dtype=torch.float32) if param_mask else None
-    if grad_q is None and grad_ops is None:
+    grad_ops, scratch = _grad_ops(lib, "drm_fk_backward_scratch_floats", (B, prog.capacity), prog, ops_f, dev, param_mask, want_grad_q)
+    if scratch is None:
         return None, None
-    scratch = torch.empty(max(1, lib.drm_fk_backward_scratch_floats(B, prog.capacity)), device=dev, dtype=torch.float32)
     if param_mask:
         _ticket(prog, dev)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    with _on_device(dev):
-        _check(lib.drm_fk_backward(ctypes.byref(walk), q.data_ptr(), B, n_targets, grad_pos.data_ptr(),
-                                   grad_rot.data_ptr() if grad_rot is not None else None,
-                                   ctypes.c_uint64(param_mask), grad_q.data_ptr() if want_grad_q else None,
-                                   grad_ops.data_ptr() if param_mask else None, scratch.data_ptr(), _stream(dev)), lib)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    _launch(lib, lib.drm_fk_backward, dev, walk, _ptr(q), B, n_targets, _ptr(grad_pos), _ptr(grad_rot), param_mask, _ptr(grad_q),
+            _ptr(grad_ops), _ptr(scratch))
     return grad_q, grad_ops
 
 
@@ -1588,19 +1432,13 @@ def fk_mse(prog: WalkProgram, ops_f, ops_i, q, target, n_dofs: int, param_mask: 
     lib = _lib_of(q, "q", ops_f)
     q = _dev_f32(q, "q", n_dofs)
     target = _dev_f32(target, "target", 3)
-    B, dev = q.shape[0], q.device
-    if target.shape[0] != B:
-        raise ValueError("q and target batch sizes differ")
+    B, dev = _same_batch("q and target batch sizes differ", q, target), q.device
     loss = torch.empty((), device=dev, dtype=torch.float32)
     grad_q = torch.empty(B, n_dofs, device=dev, dtype=torch.float32) if want_grad_q else None
-    grad_ops = torch.empty(prog.capacity, ops_f.shape[1], device=dev, dtype=torch.float32) if param_mask else None
-    scratch = torch.empty(max(1, lib.drm_fk_mse_scratch_floats(B, prog.capacity)), device=dev, dtype=torch.float32)
+    grad_ops, scratch = _grad_ops(lib, "drm_fk_mse_scratch_floats", (B, prog.capacity), prog, ops_f, dev, param_mask, True)
     _ticket(prog, dev)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    with _on_device(dev):
-        _check(lib.drm_fk_mse(ctypes.byref(walk), q.data_ptr(), target.data_ptr(), B, ctypes.c_uint64(param_mask), loss.data_ptr(),
-                              grad_q.data_ptr() if want_grad_q else None, grad_ops.data_ptr() if param_mask else None,
-                              scratch.data_ptr(), _stream(dev)), lib)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    _launch(lib, lib.drm_fk_mse, dev, walk, _ptr(q), _ptr(target), B, param_mask, _ptr(loss), _ptr(grad_q), _ptr(grad_ops), _ptr(scratch))
     return loss, grad_q, grad_ops
 
 
@@ -1613,9 +1451,7 @@ def fk_mse_links(prog: WalkProgram, base, ops_i, sel, gsign, pieces, q, target, 
     lib = _lib_of(q, "q", base)
     q = _dev_f32(q, "q", n_dofs)
     target = _dev_f32(target, "target", 3)
-    B, dev = q.shape[0], q.device
-    if target.shape[0] != B:
-        raise ValueError("q and target batch sizes differ")
+    B, dev = _same_batch("q and target batch sizes differ", q, target), q.device
     n_links, rest = divmod(len(pieces), 6)
     if rest or not 1 <= n_links <= FK_MSE_MAX_LINKS:
         raise KernelUnsupported("drm_fk_mse_links takes 1 .. %d learnable links" % FK_MSE_MAX_LINKS)
@@ -1639,11 +1475,9 @@ def fk_mse_links(prog: WalkProgram, base, ops_i, sel, gsign, pieces, q, target, 
     cached = getattr(prog, "_ws_links", None)      # (its own slot: _walk_struct keeps the struct of the LIVE table of this program)
     if cached is None or cached[0] != key:
         cached = prog._ws_links = (key, _walk_struct_build(prog, table, ops_i, n_dofs))
-    walk = cached[1]
-    with _on_device(dev):
-        _check(lib.drm_fk_mse_links(ctypes.byref(walk), sel.data_ptr(), gsign.data_ptr(), links, n_links, q.data_ptr(), target.data_ptr(), B,
-                                    ctypes.c_uint64(param_mask), loss.data_ptr(), grad_q.data_ptr() if want_grad_q else None,
-                                    grad_params.data_ptr(), scratch.data_ptr(), _stream(dev)), lib)
+    walk = _ref(cached[1])
+    _launch(lib, lib.drm_fk_mse_links, dev, walk, _ptr(sel), _ptr(gsign), links, n_links, _ptr(q), _ptr(target), B, param_mask,
+            _ptr(loss), _ptr(grad_q), _ptr(grad_params), _ptr(scratch))
     del keep
     return loss, grad_q, grad_params
 
@@ -1660,19 +1494,20 @@ def fk_jacobian_backward(prog: WalkProgram, ops_f, ops_i, q, grad_pos, grad_lin,
     grad_pos = _dev_f32(grad_pos.reshape(B, 3), "grad_pos", 3) if grad_pos is not None else None
     grad_rot = _dev_f32(grad_rot.reshape(B, 9), "grad_rot", 9) if grad_rot is not None else None
     grad_q = torch.empty(B, n_dofs, device=dev, dtype=torch.float32) if want_grad_q else None
-    grad_ops = torch.empty(prog.capacity, ops_f.shape[1], device=dev, dtype=torch.float32) if param_mask else None
-    if grad_q is None and grad_ops is None:
+    grad_ops, scratch = _grad_ops(lib, "drm_fk_backward_scratch_floats", (B, prog.capacity), prog, ops_f, dev, param_mask, want_grad_q)
+    if scratch is None:
         return None, None
-    scratch = torch.empty(max(1, lib.drm_fk_backward_scratch_floats(B, prog.capacity)), device=dev, dtype=torch.float32)
-    walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-    with _on_device(dev):
-        _check(lib.drm_fk_jacobian_backward(ctypes.byref(walk), q.data_ptr(), B,
-                                            grad_pos.data_ptr() if grad_pos is not None else None,
-                                            grad_rot.data_ptr() if grad_rot is not None else None, grad_lin.data_ptr(),
-                                            grad_ang.data_ptr(), ctypes.c_uint64(param_mask),
-                                            grad_q.data_ptr() if want_grad_q else None,
-                                            grad_ops.data_ptr() if param_mask else None, scratch.data_ptr(), _stream(dev)), lib)
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    _launch(lib, lib.drm_fk_jacobian_backward, dev, walk, _ptr(q), B, _ptr(grad_pos), _ptr(grad_rot), _ptr(grad_lin), _ptr(grad_ang),
+            param_mask, _ptr(grad_q), _ptr(grad_ops), _ptr(scratch))
     return grad_q, grad_ops
+
+
+def _plan_states(q, qd, qdd, n_dofs: int):
+    """(q, qd, qdd or None, B): the state buffers of a dynamics plan, the caller's own (_plan_input), of one batch size."""
+    q, qd = _plan_input(q, "q", n_dofs), _plan_input(qd, "qd", n_dofs)
+    qdd = _plan_input(qdd, "qdd", n_dofs) if qdd is not None else None
+    return q, qd, qdd, _same_batch("q / qd / qdd batch sizes differ", q, qd, qdd)
 
 
 def _plan_stream(stream, device):
@@ -1699,9 +1534,7 @@ class FkJacobianPlan(object):
         self.ang = torch.empty(B, 3, n_dofs, device=dev)
         self._keep = (ops_f, ops_i)
         self._walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-        self._args = (ctypes.byref(self._walk), self.q.data_ptr(), B,
-                      self.pos.data_ptr() if want_pose else None, self.quat.data_ptr() if want_pose else None,
-                      self.lin.data_ptr(), self.ang.data_ptr())
+        self._args = (_ref(self._walk), _ptr(self.q), B, _ptr(self.pos), _ptr(self.quat), _ptr(self.lin), _ptr(self.ang))
         self.batch = B
         self.device = dev
 
@@ -1737,7 +1570,7 @@ def fk_rnea(tree, chain, target_op: int, q, qd, qdd, include_gravity: bool, use_
         return None
     lib = _lib_of(q, "q", tree[1])
     wt, wc = _walk_struct(tree[0], tree[1], tree[2], n_dofs), _walk_struct(chain[0], chain[1], chain[2], n_dofs)
-    flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
+    flags = _rnea_flags(include_gravity, use_damping)
     with _on_device(q.device):
         tau, pos, quat, rc = fast.fk_rnea(_fn_addr(lib, "drm_fk_rnea"), _fn_addr(lib, "drm_rnea_scratch_floats_aligned"), ctypes.addressof(wt),
                                           ctypes.addressof(wc), int(target_op), q, qd, qdd, n_dofs, flags, _stream_int(q.device))
@@ -1759,11 +1592,8 @@ class FkInverseDynamicsPlan(object):
         # put: a DrmPut (distributed.PeerGather.put()) — every launch also writes its rows into the peers' gathered arrays
         # (drm_fk_rnea_put: the one-sided gather of a batch sharded over the GPUs of a node)
         self._lib = _lib_of(q, "q", tree[1])
-        self.q, self.qd = _plan_input(q, "q", n_dofs), _plan_input(qd, "qd", n_dofs)
-        self.qdd = _plan_input(qdd, "qdd", n_dofs) if qdd is not None else None
-        B, dev = self.q.shape[0], self.q.device
-        if self.qd.shape[0] != B or (self.qdd is not None and self.qdd.shape[0] != B):
-            raise ValueError("q / qd / qdd batch sizes differ")
+        self.q, self.qd, self.qdd, B = _plan_states(q, qd, qdd, n_dofs)
+        dev = self.q.device
         if outputs is None:
             self.tau = torch.empty(B, n_dofs, device=dev)
             self.pos = torch.empty(B, 3, device=dev)
@@ -1778,12 +1608,10 @@ class FkInverseDynamicsPlan(object):
         self._keep = (tree[1], tree[2], chain[1], chain[2])
         self._tree = _walk_struct(tree[0], tree[1].detach(), tree[2], n_dofs)
         self._chain = _walk_struct(chain[0], chain[1].detach(), chain[2], n_dofs)
-        flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
-        self._scratch = _rnea_scratch(self._lib, self._tree, B, dev)
-        self._args = (ctypes.byref(self._tree), ctypes.byref(self._chain), int(target_op), self.q.data_ptr(),
-                      self.qd.data_ptr(), self.qdd.data_ptr() if self.qdd is not None else None, B, flags,
-                      self.tau.data_ptr(), self.pos.data_ptr(), self.quat.data_ptr(),
-                      self._scratch.data_ptr() if self._scratch is not None else None)
+        flags = _rnea_flags(include_gravity, use_damping)
+        self._scratch = _scratch(self._lib, "drm_rnea", (_ref(self._tree),), B, False, dev)
+        self._args = (_ref(self._tree), _ref(self._chain), int(target_op), _ptr(self.q), _ptr(self.qd), _ptr(self.qdd), B, flags,
+                      _ptr(self.tau), _ptr(self.pos), _ptr(self.quat), _ptr(self._scratch))
         self.batch, self.device = B, dev
         self._put = put
 
@@ -1805,19 +1633,14 @@ class InverseDynamicsPlan(object):
 
     def __init__(self, prog: WalkProgram, ops_f, ops_i, q, qd, qdd, include_gravity: bool, use_damping: bool, n_dofs: int):
         self._lib = _lib_of(q, "q", ops_f)
-        self.q, self.qd = _plan_input(q, "q", n_dofs), _plan_input(qd, "qd", n_dofs)
-        self.qdd = _plan_input(qdd, "qdd", n_dofs) if qdd is not None else None
-        B, dev = self.q.shape[0], self.q.device
-        if self.qd.shape[0] != B or (self.qdd is not None and self.qdd.shape[0] != B):
-            raise ValueError("q / qd / qdd batch sizes differ")
+        self.q, self.qd, self.qdd, B = _plan_states(q, qd, qdd, n_dofs)
+        dev = self.q.device
         self.tau = torch.empty(B, n_dofs, device=dev)
         self._keep = (ops_f, ops_i)
         self._walk = _walk_struct(prog, ops_f.detach(), ops_i, n_dofs)
-        flags = (RNEA_GRAVITY if include_gravity else 0) | (RNEA_DAMPING if use_damping else 0)
-        self._scratch = _rnea_scratch(self._lib, self._walk, B, dev)
-        self._args = (ctypes.byref(self._walk), self.q.data_ptr(), self.qd.data_ptr(),
-                      self.qdd.data_ptr() if self.qdd is not None else None, B, flags, self.tau.data_ptr(),
-                      self._scratch.data_ptr() if self._scratch is not None else None)
+        flags = _rnea_flags(include_gravity, use_damping)
+        self._scratch = _scratch(self._lib, "drm_rnea", (_ref(self._walk),), B, False, dev)
+        self._args = (_ref(self._walk), _ptr(self.q), _ptr(self.qd), _ptr(self.qdd), B, flags, _ptr(self.tau), _ptr(self._scratch))
         self.batch, self.device = B, dev
 
     def launch(self, stream=None):

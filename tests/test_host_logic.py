@@ -246,6 +246,52 @@ def test_library_exports_every_declared_symbol():
     assert lib.drm_abi_version() == backend.ABI_VERSION == int(re.search(r"#define DRM_ABI_VERSION (\d+)", header).group(1))
 
 
+def header_prototypes():
+    """name -> (return type, [argument declarations]) of every drm_* function include/drm_hip.h declares, comments stripped."""
+    header = open(os.path.join(ROOT, "include", "drm_hip.h")).read()
+    header = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", header, flags=re.S))
+    found = {}
+    for ret, name, args in re.findall(r"\b(int|int64_t|const\s+char\s*\*)\s*(drm_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", header):
+        assert name not in found, name
+        args = " ".join(args.split())
+        found[name] = (" ".join(ret.replace("*", " * ").split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
+    return found
+
+
+def test_prototype_table_agrees_with_the_header():
+    """backend.PROTOTYPES is what ctypes converts every argument by: a width or an argument count that differs from the header
+    truncates or shifts a call silently.  Per function: the return type, the number of arguments, and for each argument int32_t /
+    int64_t / uint64_t / float exactly, a pointer as a pointer — and a pointer to one of the header's structs as POINTER(mirror)
+    (struct drm_walk -> DrmWalk, ...), not as an untyped one."""
+    protos = header_prototypes()
+    assert set(protos) == set(backend.PROTOTYPES), set(protos) ^ set(backend.PROTOTYPES)
+    returns = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
+    mirror = lambda struct: "".join(part.capitalize() for part in struct.split("_"))      # drm_contact_plane -> DrmContactPlane
+    assert ctypes.sizeof(ctypes.c_int) == 4
+    wrong = []
+    for name, (ret, args) in sorted(protos.items()):
+        restype, argtypes = backend.PROTOTYPES[name]
+        if restype is not returns[ret]:
+            wrong.append("%s returns %s, declared %s" % (name, ret, restype))
+        if len(argtypes) != len(args):
+            wrong.append("%s takes %d arguments, declared %d" % (name, len(args), len(argtypes)))
+            continue
+        for i, (decl, ctype) in enumerate(zip(args, argtypes)):
+            words = decl.replace("*", " * ").split()
+            words = [w for w in words if w not in ("const", "struct")]
+            if "*" not in words:
+                assert words[0] in scalars, (name, decl)
+                ok = ctype is scalars[words[0]]
+            elif words[0].startswith("drm_"):
+                ok = ctype is ctypes.POINTER(getattr(backend, mirror(words[0])))
+            else:      # void *, float *, char *, hipStream_t-as-void *: any pointer type
+                ok = ctype in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, ctypes._Pointer))
+            if not ok:
+                wrong.append("%s argument %d: header `%s`, declared %s" % (name, i, decl, ctype))
+    assert not wrong, "\n".join(wrong)
+
+
 def test_abi_argument_errors_need_no_gpu():
     lib = backend.load_library()
     assert lib.drm_fk_jacobian(None, None, 1, None, None, None, None, None) == -1
@@ -265,8 +311,6 @@ def test_rnea_backward_scratch_covers_the_fanned_out_launch():
     fans a hand's fingers out over wavefronts writes one per tile AND segment (up to 8), capped at 2048: a query sized for
     one row per tile let that launch write past the scratch buffer (caught as an intermittent GPU fault at B = 700)."""
     lib = backend.load_library()
-    lib.drm_rnea_backward_scratch_floats.restype = ctypes.c_int64
-    lib.drm_rnea_backward_scratch_floats.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     cap, n = 20, 16
     for B in (1, 64, 700, 65536, 1 << 20):
         tiles = (B + 63) // 64
