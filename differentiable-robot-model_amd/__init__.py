@@ -19,6 +19,8 @@ from .robot_model import (  # noqa: F401
     EnergyDerivatives,
     Energy,
     LinkMotion,
+    CenterOfMass,
+    BaseWrench,
     PlaneContact,
     JointLimitSprings,
     ContactTorques,

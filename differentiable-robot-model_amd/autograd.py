@@ -731,6 +731,58 @@ class _Energy(torch.autograd.Function):
         return grad_q, grad_qd, None, None, None, None
 
 
+class _WholeBodyFirstOrderOnly(_FirstOrderOnly):
+    """_FirstOrderOnly for the gradients of the centre of mass (_CenterOfMass): correct to first order, refuses to be differentiated."""
+
+    @staticmethod
+    def backward(ctx, _):
+        raise NotImplementedError(
+            "compute_center_of_mass is a first-order node (its backward contracts the CoM Jacobian with the cotangent): for second "
+            "derivatives compose the centre of mass from model.compute_forward_kinematics_all_links and the link masses")
+
+
+class _CenterOfMass(torch.autograd.Function):
+    """The outputs of backend.whole_body named by ``want`` (csrc/drm_whole_body.hip), in WHOLE_BODY_OUTPUTS' order, None for the others.
+    com is differentiable in q and com_vel in qd, both through the CoM Jacobian J [B, 3, n]:
+        grad_q = J^T g_com,      grad_qd = J^T g_com_vel.
+    J is the forward launch's where ``want`` names it; otherwise the backward launches the same call for com_jac alone.  Every other
+    output is marked non-differentiable, and the q-gradient of com_vel is not formed.  First order only: under create_graph=True the
+    gradients are first-order gradients that refuse a second differentiation (_WholeBodyFirstOrderOnly).  The walk's table is a
+    constant of the node: no history flows to learnable link parameters."""
+
+    @staticmethod
+    def forward(ctx, q, qd, qdd, prog, ops_f, ops_i, n_dofs, want, base_share, composed):
+        outs = backend.whole_body(prog, ops_f, ops_i, q.detach(), qd.detach() if qd is not None else None,
+                                  qdd.detach() if qdd is not None else None, n_dofs, want, base_share=base_share, composed=composed)
+        com, com_vel, com_acc, com_jac, ang_mom, force, moment = outs
+        ctx.call = (prog, ops_f, ops_i, n_dofs, base_share, composed)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q.detach(), *([com_jac] if com_jac is not None else []))
+        ctx.dtypes = (q.dtype, qd.dtype if qd is not None else None)
+        ctx.mark_non_differentiable(*[t for t in (com_acc, com_jac, ang_mom, force, moment) if t is not None])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_com, g_vel, *_):
+        q, *jac = ctx.saved_tensors
+        second = torch.is_grad_enabled()          # create_graph=True: first-order gradients that say so when differentiated again
+        grad_q = grad_qd = None
+        with torch.no_grad():
+            if jac:
+                J = jac[0]
+            else:
+                prog, ops_f, ops_i, n_dofs, base_share, composed = ctx.call
+                J = backend.whole_body(prog, ops_f, ops_i, q, None, None, n_dofs, ("com_jac",), base_share=base_share, composed=composed)[3]
+            if ctx.needs_input_grad[0] and g_com is not None:
+                grad_q = torch.einsum("bi,bin->bn", g_com.to(torch.float32), J).to(ctx.dtypes[0])
+            if ctx.needs_input_grad[1] and g_vel is not None:
+                grad_qd = torch.einsum("bi,bin->bn", g_vel.to(torch.float32), J).to(ctx.dtypes[1])
+        if second:
+            with torch.enable_grad():
+                grad_q, grad_qd = (_WholeBodyFirstOrderOnly.apply(g.requires_grad_(True)) if g is not None else None for g in (grad_q, grad_qd))
+        return (grad_q, grad_qd) + (None,) * 8
+
+
 class _CollisionCost(torch.autograd.Function):
     """(cost [B], dcost_dq [B, n]) of backend.collision_cost (csrc/drm_collision.hip).  The forward launch hands out the gradient with
     the cost, so the backward launches nothing: grad_q = g[:, None] * dcost_dq.  dcost_dq itself is not differentiable.  First order

@@ -33,6 +33,7 @@ LAGRANGIAN_COMPOSED = 128     # include/drm_hip.h DRM_LAGRANGIAN_COMPOSED
 IDD_COMPOSED = 256            # include/drm_hip.h DRM_IDD_COMPOSED
 ENERGY_COMPOSED = 512         # include/drm_hip.h DRM_ENERGY_COMPOSED
 LINKS_COMPOSED = 1024         # include/drm_hip.h DRM_LINKS_COMPOSED
+WHOLE_BODY_COMPOSED = 2048    # include/drm_hip_whole_body.h DRM_WHOLE_BODY_COMPOSED
 REGRESSOR_COLS = 10           # columns per body: m, m c_x, m c_y, m c_z, Ixx, Ixy, Ixz, Iyy, Iyz, Izz
 SPECIAL_FK_FAN_LINKS = 9      # index of the fan-out FK kernel in drm_walk.special[] (include/drm_hip.h DRM_SPECIAL_FK_FAN_LINKS)
 WALK_TICKET = 10               # ... and of the walk's ticket word (ABI 11, DRM_WALK_TICKET): one-launch backward reductions
@@ -90,6 +91,11 @@ class DrmCollisionParams(ctypes.Structure):
 class DrmJointSprings(ctypes.Structure):
     """Mirror of ``struct drm_joint_springs`` (include/drm_hip.h)."""
     _fields_ = [("stiffness", ctypes.c_float), ("damping", ctypes.c_float)]
+
+
+class DrmBaseShare(ctypes.Structure):
+    """Mirror of ``struct drm_base_share`` (include/drm_hip_whole_body.h)."""
+    _fields_ = [("mass", ctypes.c_float), ("mc", ctypes.c_float * 3)]
 
 
 FK_MSE_MAX_LINKS = 8
@@ -183,6 +189,14 @@ for _base in ("drm_collision_cost", "drm_sphere_distances"):
     PROTOTYPES[_base + "_scratch_floats_aligned"] = (i64, [wp, i64, i32, i32, i32, i32])
 EXPORTS = tuple(PROTOTYPES)
 
+# the entry points of include/drm_hip_whole_body.h, an addition to the ABI with a header, a table and argument rules of its own
+# (tests/test_whole_body_abi.py holds the three to one another): load_library declares from this table too
+WHOLE_BODY_PROTOTYPES = {
+    "drm_whole_body": (ctypes.c_int, [wp, vp, vp, vp, i64, i32, P(DrmBaseShare), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "drm_whole_body_scratch_floats": (i64, [wp, i64]),
+    "drm_whole_body_scratch_floats_aligned": (i64, [wp, i64]),
+}
+
 
 def library_for(device):
     """The library that computes for tensors on `device`: libdrm_hip.so for a HIP device, libdrm_cpu.so for the CPU."""
@@ -219,7 +233,7 @@ def load_library(path: str = None, kind: str = "cuda"):
             lib = ctypes.CDLL(path)
         except OSError as err:
             raise NativeLibraryError("cannot load %s: %s" % (path, err))
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(WHOLE_BODY_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         if lib.drm_abi_version() != ABI_VERSION:
@@ -1129,6 +1143,35 @@ def energy(prog: WalkProgram, ops_f, ops_i, q, qd, n_dofs: int, want=ENERGY_OUTP
     kinetic, potential, momentum, dkinetic_dq, gravity = outs
     _launch(lib, lib.drm_energy, q.device, walk, _ptr(q), _ptr(qd), B, ENERGY_COMPOSED if composed else 0, _ptr(kinetic),
             _ptr(potential), _ptr(momentum), _ptr(dkinetic_dq), _ptr(gravity), _ptr(scratch))
+    return outs
+
+
+WHOLE_BODY_OUTPUTS = ("com", "com_vel", "com_acc", "com_jac", "ang_mom", "force", "moment")
+
+
+def whole_body(prog: WalkProgram, ops_f, ops_i, q, qd, qdd, n_dofs: int, want, base_share=None, include_gravity: bool = True,
+               composed: bool = False):
+    """(com, com_vel, com_acc [B, 3], com_jac [B, 3, n], ang_mom, force, moment [B, 3]) of one launch over the whole-tree dynamics walk
+    (include/drm_hip_whole_body.h drm_whole_body): the centre of mass, its velocity, acceleration and Jacobian, the angular momentum
+    about the base origin and the wrench the mount applies to the base link.  ``qd`` / ``qdd`` None: zero.  ``want`` names the outputs
+    to compute (WHOLE_BODY_OUTPUTS); the others come back as None, neither stored nor, where that saves work, formed.  ``base_share``:
+    (mass, (mc_x, mc_y, mc_z)) of the bodies no joint moves, None to leave them out.  ``include_gravity`` applies to the wrench only.
+    ``composed`` (or DRM_WHOLE_BODY_COMPOSED=1 in the environment) forces the general kernel on every row (tests, A/B)."""
+    lib = _lib_of(q, "q", ops_f)
+    q = _dev_f32(q, "q", n_dofs)
+    qd = _dev_f32(qd, "qd", n_dofs) if qd is not None else None
+    qdd = _dev_f32(qdd, "qdd", n_dofs) if qdd is not None else None
+    B = _same_batch("q / qd / qdd batch sizes differ", q, qd, qdd)
+    outs = _wanted(want, WHOLE_BODY_OUTPUTS, [(B, 3), (B, 3), (B, 3), (B, 3, n_dofs), (B, 3), (B, 3), (B, 3)], q.device)
+    if B == 0:
+        return outs
+    composed = _composed(composed, "WHOLE_BODY")
+    base = DrmBaseShare(float(base_share[0]), (ctypes.c_float * 3)(*[float(x) for x in base_share[1]])) if base_share is not None else None
+    walk = _ref(_walk_struct(prog, ops_f.detach(), ops_i, n_dofs))
+    scratch = _scratch(lib, "drm_whole_body", (walk,), B, composed, q.device)
+    flags = (RNEA_GRAVITY if include_gravity else 0) | (WHOLE_BODY_COMPOSED if composed else 0)
+    _launch(lib, lib.drm_whole_body, q.device, walk, _ptr(q), _ptr(qd), _ptr(qdd), B, flags, _ref(base), *[_ptr(o) for o in outs],
+            _ptr(scratch))
     return outs
 
 

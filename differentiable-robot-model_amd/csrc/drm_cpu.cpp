@@ -41,6 +41,8 @@ namespace drm {
 int fail(int code, const char *fmt, const char *a = "", long b = 0, long c = 0);
 }
 #include "drm_args.hpp"
+#include "drm_args_whole_body.hpp"
+#include "drm_whole_body.hpp"
 
 namespace {
 using namespace drm_host;
@@ -1151,6 +1153,95 @@ int drm_fk_mse_links(const drm_walk *w, const int32_t *sel, const float *gsign, 
     if (int rc = drm_walk_table_backward(params, n_links, gops.data(), sel, gsign, entries, grad_params, nullptr)) return rc;
     for (int l = 0; l < n_links; ++l)
         for (int i = 6; i < LINK_PARAM_FLOATS; ++i) grad_params[l * LINK_PARAM_FLOATS + i] = 0.0f;
+    return DRM_OK;
+}
+} // extern "C"
+
+// ---- include/drm_hip_whole_body.h ---------------------------------------------------------------------------------------------------
+namespace {
+// the walks drm_whole_body.hip's fused kernel takes.  The host build runs its straight-line arithmetic (drm_whole_body.hpp
+// whole_body_chain_trig) on every row of such a call, the general walk with DRM_WHOLE_BODY_COMPOSED.
+bool whole_body_chain_walk(const drm_walk *w, int flags) {
+    return !(flags & DRM_WHOLE_BODY_COMPOSED) && (w->shape & DRM_WALK_ARM_CHAIN) && w->capacity == 8 && w->n_dofs == 7;
+}
+// drm_whole_body, rows [b0, b0 + rows): drm_whole_body.hpp's walk of the row, its records on this thread's heap
+template <int LEVEL>
+void whole_body_host_rows(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t b0, int64_t rows, int flags,
+                          const float *base, float *com, float *com_vel, float *com_acc, float *com_jac, float *ang_mom, float *force,
+                          float *moment) {
+    const int n = w->n_dofs, n_ops = w->n_ops, n_slots = w->n_slots;
+    const Ctl ctl(w);
+    HostRecords<drm::wb_rec_floats(LEVEL)> rec(n_ops); HostRecords<drm::wb_slot_floats(LEVEL)> slots(n_slots);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    const bool chain = whole_body_chain_walk(w, flags), gravity = (flags & DRM_RNEA_GRAVITY) != 0;
+    const int links = w->n_ops == w->n_dofs ? 7 : 8;
+    auto row = [&](int k) { return w->ops_f + k * DRM_OPF_STRIDE; };
+    for (int64_t b = b0; b < b0 + rows; ++b) {
+        const float *qr = q + b * n, *qdr = (LEVEL >= 1 && qd) ? qd + b * n : nullptr, *qddr = (LEVEL >= 2 && qdd) ? qdd + b * n : nullptr;
+        float *jr = com_jac ? com_jac + b * 3 * n : nullptr;
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || drm::wb_bad_input(qr[d], qdr ? qdr[d] : 0.0f, qddr ? qddr[d] : 0.0f);
+        drm::WbRoot root;
+        if (chain) {
+            float qv[7], qdv[7], qddv[7], cs[7], sn[7], jac[21];
+            for (int d = 0; d < 7; ++d) {
+                qv[d] = bad ? 0.0f : qr[d];
+                qdv[d] = (bad || !qdr) ? 0.0f : qdr[d];
+                qddv[d] = (bad || !qddr) ? 0.0f : qddr[d];
+            }
+            drm::chain_trig<7>(qv, cs, sn);
+            if (jr && links == 7) drm::whole_body_chain_trig<7, 7, LEVEL, true>(row, cs, sn, qdv, qddv, jac, base[0], root);
+            else if (jr) drm::whole_body_chain_trig<8, 7, LEVEL, true>(row, cs, sn, qdv, qddv, jac, base[0], root);
+            else if (links == 7) drm::whole_body_chain_trig<7, 7, LEVEL, false>(row, cs, sn, qdv, qddv, jac, base[0], root);
+            else drm::whole_body_chain_trig<8, 7, LEVEL, false>(row, cs, sn, qdv, qddv, jac, base[0], root);
+            if (jr)
+                for (int i = 0; i < 21; ++i) jr[i] = bad ? nan : jac[i];
+        } else {
+            drm::whole_body_tree_walk<LEVEL>(
+                n_ops, w->n_segments > 1 ? w->prefix_end : 0, n_slots, ctl, row,
+                [&](int d, float &a, float &v, float &acc) {
+                    a = bad ? 0.0f : qr[d];
+                    v = (bad || !qdr) ? 0.0f : qdr[d];
+                    acc = (bad || !qddr) ? 0.0f : qddr[d];
+                },
+                [&](int k, const float *x) { rec.put(k, x); }, [&](int k, float *x) { rec.get(k, x); },
+                [&](int s, const float *x) { slots.put(s, x); }, [&](int s, float *x) { slots.get(s, x); },
+                [&](int j, const float *col) {
+                    if (j >= n || !jr) return;
+                    for (int i = 0; i < 3; ++i) jr[i * n + j] = bad ? nan : col[i];
+                },
+                base[0], root);
+        }
+        drm::WbOut o;
+        drm::wb_finish<LEVEL>(root, base, gravity, o);
+        for (int i = 0; i < 3; ++i) {
+            if (com) com[b * 3 + i] = bad ? nan : o.com[i];
+            if (LEVEL >= 1 && com_vel) com_vel[b * 3 + i] = bad ? nan : o.com_vel[i];
+            if (LEVEL >= 2 && com_acc) com_acc[b * 3 + i] = bad ? nan : o.com_acc[i];
+            if (LEVEL >= 1 && ang_mom) ang_mom[b * 3 + i] = bad ? nan : o.ang_mom[i];
+            if (force) force[b * 3 + i] = bad ? nan : o.force[i];
+            if (moment) moment[b * 3 + i] = bad ? nan : o.moment[i];
+        }
+    }
+}
+} // namespace
+
+extern "C" {
+// The centre of mass, its Jacobian, momentum and the base wrench: every row runs drm_whole_body.hpp's arithmetic — the chain form where
+// drm_whole_body.hip would launch its fused kernel, the general walk elsewhere — without the records in LDS / scratch.
+int64_t drm_whole_body_scratch_floats(const drm_walk *, int64_t) { return 0; }
+int64_t drm_whole_body_scratch_floats_aligned(const drm_walk *, int64_t) { return 0; }
+
+int drm_whole_body(const drm_walk *w, const float *q, const float *qd, const float *qdd, int64_t B, int32_t flags, const drm_base_share *base,
+                   float *com, float *com_vel, float *com_acc, float *com_jac, float *ang_mom, float *force, float *moment, float *, void *) {
+    drm::WholeBodyBase hb;
+    if (int rc = drm::args_whole_body(w, q, qd, B, base, com, com_vel, com_acc, com_jac, ang_mom, force, moment, hb)) return rc;
+    const int level = drm::whole_body_level(qd, qdd, com_vel, com_acc, ang_mom, force, moment);
+    for_chunks(B, [&](int64_t, int64_t b0, int64_t rows) {
+        if (level == 2) whole_body_host_rows<2>(w, q, qd, qdd, b0, rows, flags, hb.v, com, com_vel, com_acc, com_jac, ang_mom, force, moment);
+        else if (level == 1) whole_body_host_rows<1>(w, q, qd, qdd, b0, rows, flags, hb.v, com, com_vel, com_acc, com_jac, ang_mom, force, moment);
+        else whole_body_host_rows<0>(w, q, qd, qdd, b0, rows, flags, hb.v, com, com_vel, com_acc, com_jac, ang_mom, force, moment);
+    });
     return DRM_OK;
 }
 } // extern "C"

@@ -27,7 +27,7 @@ from . import backend
 from .flatten import (OPF_DAMP, OPF_IO, OPF_MASS, OPF_MCOM, OPF_STRIDE, OPI_OUT, OPI_PERM, _PERM, RobotSpec, WalkProgram, build_robot_spec,
                       build_walk, fold_link_table, foldable_links, identity_table_row, virtual_row_constants)
 from .autograd import (_FkJacobian, _FkMse, _FkMseLinks, _FkPositions, _ForwardDynamics, _InverseDynamics, _MassMatrix,  # noqa: F401
-                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _CollisionCost, _ContactTorques, _ContactRollout,
+                       _ForwardDynamicsRollout, _Energy, _LinkAdjoint, _CollisionCost, _CenterOfMass, _ContactTorques, _ContactRollout,
                        _quat_grad_to_rot)
 from .rigid_body import DifferentiableRigidBody, LinkPose, LinkVelocity
 from .urdf_utils import URDFRobotModel
@@ -156,6 +156,24 @@ class Energy(NamedTuple):
     """What DifferentiableRobotModel.compute_energy returns: differentiable once with respect to q and qd."""
     kinetic: torch.Tensor               # [B]
     potential: torch.Tensor             # [B]
+
+
+class CenterOfMass(NamedTuple):
+    """What DifferentiableRobotModel.compute_center_of_mass returns: base axes; ``position`` is differentiable once in q and
+    ``velocity`` once in qd, every other field carries no autograd history."""
+    mass: object                                # M: a Python float; a detached 0-dim tensor for a model with learnable links
+    position: torch.Tensor                      # [B, 3] sum m_i c_i / M
+    velocity: Optional[torch.Tensor]            # [B, 3] jacobian qd; None when qd is None
+    acceleration: Optional[torch.Tensor]        # [B, 3] d/dt velocity (gravity not included); None when qdd is None
+    jacobian: Optional[torch.Tensor]            # [B, 3, n]; None unless asked for
+    angular_momentum: Optional[torch.Tensor]    # [B, 3] about the base ORIGIN; None when qd is None
+
+
+class BaseWrench(NamedTuple):
+    """What DifferentiableRobotModel.compute_base_wrench returns (no autograd history on either field): the wrench the mount applies to
+    the base link, at the base origin in base axes."""
+    force: torch.Tensor                         # [B, 3]
+    moment: torch.Tensor                        # [B, 3]
 
 
 class LinkMotion(NamedTuple):
@@ -2007,6 +2025,143 @@ class DifferentiableRobotModel(torch.nn.Module):
             return _Energy.apply(q, qd, dw.program, ops_f, dw.ops_i, self._n_dofs)
         with torch.no_grad():
             return backend.energy(dw.program, ops_f, dw.ops_i, q.detach(), qd.detach(), self._n_dofs, want=("kinetic", "potential"))[:2]
+
+    # ------------------------------------------------------------------ the robot as a whole
+    def _moved_links(self) -> np.ndarray:
+        """bool [L]: at least one moving joint on the way from the root to the link."""
+        have = self.__dict__.get("_moved_mask")
+        if have is None:
+            spec = self._spec
+            have = self.__dict__["_moved_mask"] = np.array([any(spec.dof[j] >= 0 for j in spec.chain_to(i)) for i in range(spec.n_links)])
+        return have
+
+    def _base_share(self):
+        """(mass, (mc_x, mc_y, mc_z)) of the links no joint moves — the base and whatever is fixed to it — in the base frame: fp64 on
+        the host from the constant link table, the fixed transforms composed as flatten.fold_link_table composes them.  Once per set
+        of learnable parameters; a learnable mass, com, trans or rot_angles on one of these links is refused."""
+        have = self.__dict__.get("_base_share_cache")
+        if have is not None and have[0] == self._learnable_version:
+            return have[1]
+        spec, moved = self._spec, self._moved_links()
+        for link, name in self._learnable:
+            if not moved[link] and name in ("mass", "com", "trans", "rot_angles"):
+                raise NotImplementedError("%s of %s is learnable and the link belongs to the base share (no joint moves it): "
+                                          "pass include_base=False" % (name, spec.link_names[link]))
+        if self._static_table is None:
+            self._link_table()
+        rows = self._static_table[:spec.n_links].detach().cpu().numpy().astype(np.float64)
+        F, t = rows[:, 0:9].reshape(-1, 3, 3), rows[:, 9:12]      # (the link table's rows: F row-major, then t; flatten.OPF_F / OPF_T)
+        R, p = [None] * spec.n_links, [None] * spec.n_links
+        mass, mc = 0.0, np.zeros(3)
+        for i in range(spec.n_links):      # children come after their parents in URDF <link> order
+            if moved[i]:
+                continue
+            par = int(spec.parent[i])
+            Rp, pp = (np.eye(3), np.zeros(3)) if par < 0 else (R[par], p[par])
+            R[i], p[i] = Rp @ F[i], Rp @ t[i] + pp
+            mass += rows[i, OPF_MASS]
+            mc += R[i] @ rows[i, OPF_MCOM:OPF_MCOM + 3] + rows[i, OPF_MASS] * p[i]
+        share = (float(mass), tuple(float(x) for x in mc))
+        self.__dict__["_base_share_cache"] = (self._learnable_version, share)
+        return share
+
+    def total_mass(self, include_base: bool = True):
+        """M = sum of the link masses: over every link, or with ``include_base=False`` over the links that a joint moves.  A Python
+        float for a constant model; for a model with learnable links a detached 0-dim tensor of their current values."""
+        moved = self._moved_links()
+        base = self._base_share()[0] if include_base else 0.0
+        if not self._learnable:
+            have = self.__dict__.setdefault("_total_mass_cache", {})      # (a constant model: once, not a device read per call)
+            if bool(include_base) not in have:
+                if self._static_table is None:
+                    self._link_table()
+                m = self._static_table[:self._spec.n_links, OPF_MASS].detach().cpu().numpy().astype(np.float64)
+                have[bool(include_base)] = float((m * moved).sum() + base)
+            return have[bool(include_base)]
+        with torch.no_grad():
+            m = self._link_table()[:self._spec.n_links, OPF_MASS].detach().to(torch.float64)
+            return ((m * torch.from_numpy(moved).to(m.device)).sum() + base).to(torch.float32)
+
+    def _whole_body_mass(self, include_base: bool):
+        """total_mass, refused where it is zero (a constant model; a learnable model's lives on the device and is not read back: its
+        rows come out NaN)"""
+        mass = self.total_mass(include_base)
+        if not self._learnable and not mass > 0.0:
+            raise ValueError("the robot's total mass is zero: it has no centre of mass")
+        return mass
+
+    def compute_center_of_mass(self, q: torch.Tensor, qd: Optional[torch.Tensor] = None, qdd: Optional[torch.Tensor] = None, *,
+                               jacobian: bool = False, include_base: bool = True, _composed: bool = False) -> CenterOfMass:
+        """Where the robot's centre of mass is and how it moves, at q [B, n] (qd, qdd [B, n] optional), in base axes (z up):
+            mass              M = total_mass(include_base)
+            position          [B, 3]     sum m_i c_i / M over the links (c_i the world position of link i's centre of mass)
+            velocity          [B, 3]     jacobian qd; the linear momentum is M velocity.  None without qd.
+            acceleration      [B, 3]     d/dt velocity, gravity not included; needs qd.  None without qdd.
+            jacobian          [B, 3, n]  d position / d q.  jacobian^T (0, 0, M g) = compute_energy_derivatives(q, qd).gravity.
+                                         None unless ``jacobian=True``.
+            angular_momentum  [B, 3]     sum (c_i x m_i v_ci + I_i w_i): about the base ORIGIN.  About the centre of mass it is
+                                         angular_momentum - position x M velocity.  None without qd.
+        The links that no joint moves — the base and whatever is fixed to it — enter ``mass`` and ``position`` as a constant (the
+        base share); ``include_base=False`` leaves them out of both.
+
+        One kernel launch (csrc/drm_whole_body.hip; two with a ragged tail): one sweep out and one back over the tree that keeps what
+        inverse dynamics and compute_energy_derivatives carry to the root and drop there.  Only the levels the requested outputs need
+        are computed.  A 7-DoF arm's full 64-row tiles run a kernel that keeps everything in registers; every other robot one lane
+        per row over the ops of its walk.  Argument handling is that of compute_energy_derivatives (unbatched inputs give unbatched
+        results); works for models on the CPU and on a HIP device, with either joint model and for models with learnable links:
+        their current values are used, ``mass`` is then a detached 0-dim tensor, and a learnable mass, com, trans or rot_angles on a
+        link of the base share raises NotImplementedError with ``include_base=True``.  A row whose q / qd / qdd is not finite — or
+        whose |q| is beyond 1e5 — returns NaN in every field and changes no bit of any other row.
+
+        ``position`` is differentiable with respect to q and ``velocity`` with respect to qd, FIRST order only, through one autograd
+        node whose backward launches the same call for the Jacobian and contracts it with the cotangent; a second backward raises.
+        The q-gradient of ``velocity`` is not formed.  ``acceleration``, ``jacobian`` and ``angular_momentum`` carry NO autograd
+        history, whatever requires grad, and no history flows to learnable link parameters.  (``_composed``, or
+        DRM_WHOLE_BODY_COMPOSED=1 in the environment: every row takes the general kernel; for tests and A/B measurements.)"""
+        if qdd is not None and qd is None:
+            raise ValueError("the acceleration of the centre of mass needs qd")
+        mass = self._whole_body_mass(include_base)
+        want = ["com"] + (["com_vel", "ang_mom"] if qd is not None else []) + (["com_acc"] if qdd is not None else []) + \
+            (["com_jac"] if jacobian else [])
+        base = self._base_share() if include_base else None
+        com, vel, acc, jac, ang, _, _ = self._compute_whole_body(q, qd, qdd, tuple(want), base, True, bool(_composed), True)
+        return CenterOfMass(mass, com, vel, acc, jac, ang)
+
+    def compute_base_wrench(self, q: torch.Tensor, qd: Optional[torch.Tensor] = None, qdd: Optional[torch.Tensor] = None, *,
+                            include_gravity: bool = True, include_base: bool = True, _composed: bool = False) -> BaseWrench:
+        """The wrench the mount applies to the base link — at the base origin, in base axes — that keeps the base at rest while the
+        robot moves through (q, qd, qdd) [B, n]: the root wrench that inverse dynamics carries down the tree and drops.
+            force   [B, 3]  sum m_i a_ci + M g e_z
+            moment  [B, 3]  sum (c_i x m_i a_ci + I_i al_i + w_i x I_i w_i) + (sum m_i c_i) x g e_z
+        qd / qdd None: zero; with both None it is the static wrench.  ``include_gravity=False`` drops the two weight terms;
+        ``include_base=False`` leaves the weight of the links that no joint moves out of them.  Joint damping does not enter.  The
+        wrench the robot applies to its mount is the negative; the zero-moment point on the plane z = 0 is
+        (-moment_y / force_z, moment_x / force_z) — what a force plate or a base force/torque sensor reads, and what tip-over
+        margins of a mobile manipulator are computed from.
+
+        One launch, batching, devices, learnable links and non-finite rows as for compute_center_of_mass.  The results carry NO
+        autograd history, whatever requires grad."""
+        self._whole_body_mass(include_base)
+        base = self._base_share() if include_base else None
+        outs = self._compute_whole_body(q, qd, qdd, ("force", "moment"), base, bool(include_gravity), bool(_composed), False)
+        return BaseWrench(outs[5], outs[6])
+
+    @tensor_check
+    def _compute_whole_body(self, q, qd, qdd, want, base, gravity, composed, differentiable):
+        assert q.ndim == 2
+        assert q.shape[1] == self._n_dofs
+        for t in (qd, qdd):
+            assert t is None or (t.ndim == 2 and t.shape == q.shape)
+        self._require_device()
+        with torch.no_grad():
+            dw = self._dynamics_walk()
+            ops_f = self._ops_f(dw).detach()
+        if differentiable and torch.is_grad_enabled() and (q.requires_grad or (qd is not None and qd.requires_grad)):
+            return _CenterOfMass.apply(q, qd, qdd, dw.program, ops_f, dw.ops_i, self._n_dofs, want, base, composed)
+        with torch.no_grad():
+            return backend.whole_body(dw.program, ops_f, dw.ops_i, q.detach(), qd.detach() if qd is not None else None,
+                                      qdd.detach() if qdd is not None else None, self._n_dofs, want, base_share=base,
+                                      include_gravity=gravity, composed=composed)
 
     # ------------------------------------------------------------------ link motion and external wrenches
     def _links_plan(self, link_names):
